@@ -9,7 +9,13 @@ one deterministic workload cut into contiguous byte-balanced shards
 --scaling weak (default; config 4: strong): the job holds N x the per-GPU
 request count; strong: the job holds the config's request count, whatever N.
 
-At N = 1 the line also carries:
+A plain run sets up, warms up, times the steps and prints the result line.
+--dump-outputs DIR writes what the last timed step computed (the verdicts and
+the per-rule counters a caller of the timed path receives) as DIR/<name>.npy.
+
+--full adds the legs below to the line (each can be switched off on its own):
+  parity        an oracle sample of the timed batch's own verdicts;
+and at N = 1:
   cpu_baseline  the oracle (reference algorithm restated) on all host cores
                 and on one, bounded sample (config 5: the NFA engine);
   e2e           the host drop-in path: l7m_eval on a pinned host arena
@@ -19,7 +25,7 @@ At N = 1 the line also carries:
                 decodeHeaders call shape) from 8 / 64 / 512 caller threads:
                 verdicts/s and latency percentiles (cilium_amd/batcher_bench).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--requests R]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--requests R] [--full] [--dump-outputs DIR]
 N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 """
 import argparse
@@ -28,9 +34,11 @@ import os
 import sys
 import time
 
-import numpy as np
-import torch
-import torch.distributed as dist
+_T0 = time.perf_counter()  # log() prints seconds since here: imports count as set-up
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.distributed as dist  # noqa: E402
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -81,7 +89,47 @@ def parse():
     ap.add_argument("--extended", action="store_true",
                     help="config 2 with workloads.EXTENDED_RULES (\\b, look-ahead, back-references) in front of its "
                          "1000 rules: the slow pass (http_slow_kernel) decides the requests they may match")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs outside the headline figure: parity sample, pinned-host end-to-end, "
+                         "batcher, CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): "
+                         "the verdicts (a fixed seeded sample when they exceed the size cap) and the "
+                         "per-rule counters")
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_parity = args.no_e2e = args.no_batcher = args.no_cpu_baseline = True
+    return args
+
+
+DUMP_MAX_VERDICTS = 6_000_000  # float64: 48 MB of the 64 MB a dump may hold in all
+
+
+def sample_index(n, cap=DUMP_MAX_VERDICTS):
+    """Which of n verdicts --dump-outputs writes: all of them up to `cap`,
+    else `cap` sorted indices drawn with a fixed seed (the same for every run
+    and build with the same arguments)."""
+    if n <= cap:
+        return None
+    return np.sort(np.random.default_rng(0x17D).integers(0, n, size=cap, dtype=np.int64))
+
+
+def dump_outputs(outdir, verdicts, hits):
+    """--dump-outputs: `verdicts` maps a name to the int32 device tensor the
+    last timed step wrote (one verdict per request, request order); `hits` is
+    the per-rule hit/deny counter vector of that step (after the all-reduce).
+    Verdicts are int32 (rule index, negative code, or the allow codes next to
+    2^31) and counters are at most the request count: float64 holds both
+    exactly."""
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_MAX_VERDICTS // max(1, len(verdicts))
+    for name, v in verdicts.items():
+        idx = sample_index(v.numel(), share)
+        if idx is not None:
+            v = v[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(outdir, f"{name}.npy"), v.cpu().numpy().astype(np.float64))
+    if hits is not None:
+        np.save(os.path.join(outdir, "hits.npy"), np.asarray(hits).astype(np.float64))
 
 
 def host_cores():
@@ -271,14 +319,24 @@ def emit(res):
     from cilium_amd.codehash import code_md5
     res["code_md5"] = code_md5(L.LIB_PATH)
     print(json.dumps(res), flush=True)
+    log("result line printed")
 
 
 def log(msg):
-    print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+    print(f"[bench {time.strftime('%H:%M:%S')} +{time.perf_counter() - _T0:.1f}s] {msg}", file=sys.stderr, flush=True)
+
+
+def job_shard(cfg, n, world, rank, **kw):
+    """This rank's byte-balanced range of the job (dist.balanced_shard).  One
+    rank owns all of it: no sizing pass over the workload."""
+    if world == 1:
+        return 0, n
+    return D.balanced_shard(cfg, n, world, rank, **kw)
 
 
 def main():
     args = parse()
+    log("imports done")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -313,27 +371,26 @@ def main():
           if c["proto"] == L.PROTO_HTTP else L.RuleSet.compile_kafka(rules))
 
     # ---- rank's byte-balanced shard, generated deterministically, in HBM ----
-    lo, hi = D.balanced_shard(cfg, n_job, world, rank, threads=threads,
-                              device=dev if args.backend == "nccl" else None)
+    lo, hi = job_shard(cfg, n_job, world, rank, threads=threads,
+                       device=dev if args.backend == "nccl" else None)
     per_gpu = hi - lo
     log(f"rank {rank}: compiled {len(rules)} rules; generating requests [{lo}, {hi}) of {n_job}")
     t0 = time.perf_counter()
     arena, offs = W.requests(cfg, lo, per_gpu, threads=threads)
     gen_s = time.perf_counter() - t0
     rec_bytes = arena.nbytes - 64  # W.requests: packed (4-byte padded) records + 64 B tail pad
-    pinned = torch.from_numpy(arena).pin_memory()
+    keep_host = world == 1 and not args.no_e2e and not args.diag
+    # the pinned copy of the arena is the e2e leg's input; without that leg the arena goes up as it is
+    pinned = torch.from_numpy(arena).pin_memory() if keep_host else None
     d_arena = torch.empty(arena.nbytes, dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    d_arena.copy_(pinned, non_blocking=True)
+    d_arena.copy_(pinned if keep_host else torch.from_numpy(arena), non_blocking=True)
     torch.cuda.synchronize()
     h2d_s = time.perf_counter() - t0
     d_offs = torch.from_numpy(offs.view(np.int64)).to(dev)
     arena_nbytes = arena.nbytes
-    keep_host = world == 1 and not args.no_e2e and not args.diag
     host_offs = offs if keep_host else None
-    if not keep_host:
-        del pinned
     del arena, offs
     d_verd = torch.empty(per_gpu, dtype=torch.int32, device=dev)
     d_hits = torch.zeros(rs.n_counters, dtype=torch.int64, device=dev)
@@ -375,6 +432,9 @@ def main():
     if args.dump:
         np.savez(f"{args.dump}.rank{rank}.npz", lo=lo, hi=hi, verdicts=d_verd.cpu().numpy(),
                  hits=d_hits.cpu().numpy(), elapsed=elapsed)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"verdicts" if world == 1 else f"verdicts.rank{rank}": d_verd},
+                     d_hits.cpu().numpy() if rank == 0 else None)
 
     total_requests = n_job * args.steps
     value = total_requests / elapsed
@@ -419,7 +479,7 @@ def main():
                                      else None),
                          "kernel_ms": kavg * 1e3, "algorithmic_bytes_per_launch": alg_bytes},
             "counters_ok": hits_total == expect_hits,
-            "host": {"gen_s": gen_s, "h2d_GBps": arena_nbytes / h2d_s / 1e9},
+            "host": {"gen_s": gen_s, "h2d_GBps": arena_nbytes / h2d_s / 1e9, "h2d_pinned": keep_host},
         }
         tr = res["roofline"]["traffic"]
         # PMC HBM bytes per launch over the algorithmic bytes: > 1 = re-reads,
@@ -494,7 +554,10 @@ def run_single_process(args, scaling):
     for _ in range(args.steps):
         ds.eval_device(rs, shards, hits)
     elapsed = time.perf_counter() - t0
-    got = np.concatenate([v.cpu().numpy() for v in verd])
+    if args.dump_outputs or not args.no_parity:
+        got = np.concatenate([v.cpu().numpy() for v in verd])
+    if args.dump_outputs:  # hits accumulate over the timed steps on this path
+        dump_outputs(args.dump_outputs, {"verdicts": torch.from_numpy(got)}, hits)
     value = n_job * args.steps / elapsed
     alg = rec_bytes + 12 * n_job + 8 * rs.n_counters
     res = {
@@ -535,8 +598,8 @@ def run_mixed(args, world, rank, dev, scaling):
     n_job_part = (per_gpu // 2) * (world if scaling == "weak" else 1)
     parts = []
     for proto, gcfg, seed, n_rules in W.mixed_parts(4):
-        lo, hi = D.balanced_shard(gcfg, n_job_part, world, rank, threads=threads, seed=seed, n_rules=n_rules,
-                                  device=dev if args.backend == "nccl" else None)
+        lo, hi = job_shard(gcfg, n_job_part, world, rank, threads=threads, seed=seed, n_rules=n_rules,
+                           device=dev if args.backend == "nccl" else None)
         rules = W.rules(gcfg, seed=seed, n_rules=n_rules)
         rs = (L.RuleSet.compile_http(rules, lds_budget_bytes=args.lds_budget) if proto == L.PROTO_HTTP
               else L.RuleSet.compile_kafka(rules))
@@ -602,6 +665,10 @@ def run_mixed(args, world, rank, dev, scaling):
     alg_bytes = sum(p["rec_bytes"] + 12 * p["n"] for p in parts) + 8 * sum(n_cnt)
     achieved = alg_bytes / kavg / 1e9
     counters_ok = None if args.no_hits else int(d_hits.sum().item()) == n_job
+    if args.dump_outputs:
+        sfx = "" if world == 1 else f".rank{rank}"
+        dump_outputs(args.dump_outputs, {("verdicts_http" if p["proto"] == L.PROTO_HTTP else "verdicts_kafka") + sfx:
+                                         p["d_verd"] for p in parts}, d_hits.cpu().numpy() if rank == 0 else None)
     if rank != 0:
         dist.destroy_process_group()
         return

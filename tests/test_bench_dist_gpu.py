@@ -55,9 +55,18 @@ def test_bench_two_ranks_gloo_equals_one_rank(gpu, tmp_path, cfg, scaling, per):
     assert sh2[0]["lo"] == 0 and sh2[0]["hi"] == sh2[1]["lo"] and sh2[1]["hi"] == n_job
     v2 = np.concatenate([s["verdicts"] for s in sh2])
     # the same job on one rank
-    res1, sh1 = _bench(str(tmp_path), 1, ["--config", str(cfg), "--requests", str(n_job), "--scaling", "weak"], "one")
+    out = tmp_path / "outputs"
+    res1, sh1 = _bench(str(tmp_path), 1, ["--config", str(cfg), "--requests", str(n_job), "--scaling", "weak",
+                                          "--dump-outputs", str(out)], "one")
     assert np.array_equal(sh1[0]["verdicts"], v2)
     assert np.array_equal(sh2[0]["hits"], sh1[0]["hits"])  # all-reduced counters == one rank's
+    # --dump-outputs: the last timed step's verdicts and counters as float64 .npy (whole: under the sample cap)
+    assert sorted(os.listdir(out)) == ["hits.npy", "verdicts.npy"]
+    dv, dh = np.load(out / "verdicts.npy"), np.load(out / "hits.npy")
+    assert dv.dtype == np.float64 and dh.dtype == np.float64
+    assert np.array_equal(dv, sh1[0]["verdicts"]) and np.array_equal(dh, sh1[0]["hits"])
+    # a run without --full carries none of the extra legs
+    assert not {"parity", "e2e", "batcher", "cpu_baseline"} & set(res1) and res1["steps"] == 3
     # oracle on a strided sample of the job
     from oracle import HttpOracle, KafkaOracle
     rules = W.rules(cfg)

@@ -137,12 +137,12 @@ def test_forced_capture_backreferences_first_pass_match_oracle():
     assert len(prog.dcaps) == 1 and prog.h["n_slow"] == 1
 
 
-def test_forced_capture_analysis_differential_fuzz():
+def test_forced_capture_analysis_differential_fuzz(tmp_path):
     """tests/cpp/fuzz_dcap.cc: random P1 (C{n,m}) L2 \\1 R patterns and near
     misses; wherever regex_ecma.h analyze_dcap accepts one, the first-pass
     decision (P1, maximal class run, L2, the run repeated, R's automaton)
     equals std::regex_match on every subject."""
-    exe = "/tmp/l7m_fuzz_dcap"
+    exe = str(tmp_path / "l7m_fuzz_dcap")
     src = os.path.join(ROOT, "tests", "cpp", "fuzz_dcap.cc")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-o", exe, src,
                            os.path.join(ROOT, "cilium_amd", "csrc", "regex_ecma.cc"),
@@ -261,10 +261,10 @@ def test_compiler_edge_cases():
     assert _interp_vs_oracle(rules, arena, offs).tolist() == [0, -1]
 
 
-def test_regex_compiler_differential_fuzz():
+def test_regex_compiler_differential_fuzz(tmp_path):
     """Build and run tests/cpp/fuzz_regex.cc: the ECMAScript parser + DFA
     builder against std::regex_match on random patterns and inputs."""
-    exe = "/tmp/l7m_fuzz_regex"
+    exe = str(tmp_path / "l7m_fuzz_regex")
     src = os.path.join(ROOT, "tests", "cpp", "fuzz_regex.cc")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-o", exe, src,
                            os.path.join(ROOT, "cilium_amd", "csrc", "regex_ecma.cc"),

@@ -22,5 +22,5 @@ for cfg in 2 3 5; do
   done
 done
 bash tools/gpu_sq.sh $TAG || exit $?
-timeout -k 10 600 python3 -u bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 600 python3 -u bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench rc=$?"

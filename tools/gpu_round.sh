@@ -15,8 +15,8 @@ step() {  # name, seconds, command...
 }
 step pytest_gpu 420 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread
 rc=$?; [ $rc -le 1 ] || exit $rc
-step bench_http 420 python -u bench.py || exit 1
-step bench_kafka 420 python -u bench.py --config 3 || exit 1
+step bench_http 420 python -u bench.py --full || exit 1
+step bench_kafka 420 python -u bench.py --full --config 3 || exit 1
 step prof_http 420 rocprofv3 --kernel-trace --stats -d $PWD/$OUT/prof_http -o run --output-format csv -- python3 -u bench.py --steps 20 --warmup 2 --no-cpu-baseline || exit 1
 step prof_kafka 420 rocprofv3 --kernel-trace --stats -d $PWD/$OUT/prof_kafka -o run --output-format csv -- python3 -u bench.py --config 3 --steps 20 --warmup 2 --no-cpu-baseline || exit 1
 for c in FETCH_SIZE WRITE_SIZE; do
