@@ -731,4 +731,109 @@ uint32_t packed_walk(const PackedDfa& p, const uint8_t* s, size_t n) {
   return es;
 }
 
+bool build_dense(const PackedDfa& p, DenseDfa* out) {
+  // 1. the states reachable from the start, by packed base
+  auto target = [&](uint32_t base, uint32_t b) -> uint32_t {
+    const uint32_t e = p.table[base + b];
+    return (e & 0xffu) == b ? e >> 8 : 0u;
+  };
+  std::vector<uint32_t> bases;  // discovery order, then: multi ascending, latched ascending
+  std::vector<uint32_t> id(p.n_slots, kNoPat);  // base -> state id (kNoPat: not reached)
+  if (p.start_base) {
+    bases.push_back(p.start_base);
+    id[p.start_base] = 0;
+  }
+  for (size_t i = 0; i < bases.size(); ++i) {
+    const uint32_t base = bases[i];
+    for (uint32_t b = 0; b < 256; ++b) {
+      const uint32_t t = target(base, b);
+      if (t && id[t] == kNoPat) {
+        id[t] = 0;
+        bases.push_back(t);
+        if (bases.size() + 1 > kDenseMaxStates) return false;
+      }
+    }
+  }
+  std::sort(bases.begin(), bases.end());  // bases < region (multi-pattern) come first
+  const uint32_t nstates = static_cast<uint32_t>(bases.size()) + 1;
+  uint32_t n_multi = 0;
+  for (uint32_t i = 0; i < bases.size(); ++i) {
+    id[bases[i]] = i + 1;
+    if (bases[i] < p.region) ++n_multi;
+  }
+  const uint32_t region = n_multi + 1;
+
+  // 2. per state the (target id, latch) of every byte; byte classes by refinement
+  std::vector<uint16_t> tgt(static_cast<size_t>(nstates) * 256, 0);
+  std::vector<uint32_t> lat(static_cast<size_t>(region) * 256, kNoPat);
+  uint8_t cls[256] = {0};
+  uint32_t ncls = 1;
+  uint8_t rep[256] = {0};  // class -> its first byte
+  for (uint32_t s = 1; s < nstates; ++s) {
+    const uint32_t base = bases[s - 1];
+    uint16_t* trow = &tgt[static_cast<size_t>(s) * 256];
+    uint32_t* lrow = s < region ? &lat[static_cast<size_t>(s) * 256] : nullptr;
+    for (uint32_t b = 0; b < 256; ++b) {
+      const uint32_t t = target(base, b);
+      trow[b] = t ? static_cast<uint16_t>(id[t]) : 0;
+      if (lrow && t) lrow[b] = p.latch[base + b];
+    }
+    bool split = false;
+    for (uint32_t b = 0; b < 256 && !split; ++b) {
+      const uint32_t r = rep[cls[b]];
+      split = trow[b] != trow[r] || (lrow && lrow[b] != lrow[r]);
+    }
+    if (!split) continue;
+    // bytes of one class that this state tells apart get classes of their own
+    uint8_t ncl[256];
+    std::vector<uint32_t> first;  // new class -> its first byte
+    for (uint32_t b = 0; b < 256; ++b) {
+      uint32_t c = 0;
+      for (; c < first.size(); ++c) {
+        const uint32_t r = first[c];
+        if (cls[r] == cls[b] && trow[r] == trow[b] && (!lrow || lrow[r] == lrow[b])) break;
+      }
+      if (c == first.size()) first.push_back(b);
+      ncl[b] = static_cast<uint8_t>(c);
+    }
+    ncls = static_cast<uint32_t>(first.size());
+    std::memcpy(cls, ncl, 256);
+    for (uint32_t c = 0; c < ncls; ++c) rep[c] = static_cast<uint8_t>(first[c]);
+  }
+
+  // 3. tables
+  DenseDfa d;
+  d.nstates = nstates;
+  d.ncls = ncls;
+  std::memcpy(d.cmap, cls, 256);
+  d.table.assign(static_cast<size_t>(nstates) * ncls, 0);
+  d.es.assign(nstates, 0u);
+  d.latch.assign(static_cast<size_t>(region) * ncls, kNoPat);
+  for (uint32_t s = 1; s < nstates; ++s) {
+    d.es[s] = p.es[bases[s - 1]];
+    for (uint32_t c = 0; c < ncls; ++c) {
+      d.table[static_cast<size_t>(s) * ncls + c] = tgt[static_cast<size_t>(s) * 256 + rep[c]];
+      if (s < region) d.latch[static_cast<size_t>(s) * ncls + c] = lat[static_cast<size_t>(s) * 256 + rep[c]];
+    }
+  }
+  d.start_state = p.start_base ? id[p.start_base] : 0u;
+  d.region = region;
+  d.start_latch = p.start_latch;
+  *out = std::move(d);
+  return true;
+}
+
+uint32_t dense_walk(const DenseDfa& d, const uint8_t* s, size_t n) {
+  uint32_t st = d.start_state, last = kNoPat;
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t slot = st * d.ncls + d.cmap[s[i]];
+    last = st < d.region ? slot : last;
+    st = d.table[slot];
+  }
+  if (!st) return 0;
+  const uint32_t es = d.es[st];
+  if (es == kLatchedAccept) return kLatchedAccept | (last == kNoPat ? d.start_latch : d.latch[last]);
+  return es;
+}
+
 }  // namespace l7m

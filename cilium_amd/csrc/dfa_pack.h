@@ -88,6 +88,39 @@ re::Status build_field_dfa(const std::vector<const re::Ast*>& patterns, const Fi
 // returns the end code (0, set id, or kLatchedAccept | pattern).
 uint32_t packed_walk(const PackedDfa& p, const uint8_t* s, size_t n);
 
+// Dense class-compressed form of a finished PackedDfa (program.h kDfaDense),
+// for automata walked from HBM whose packed slot table is mostly holes: one
+// u16 target per (state, byte class).  End sets, candidate tables and pattern
+// ids are the packed automaton's.
+//
+//     cls = cmap[b]; slot = st * ncls + cls;
+//     last = st < region ? slot : last;  st = T16[slot];
+//
+// State 0 is dead (an all-zero row: a dead walk stays dead with no check),
+// the multi-pattern states (packed base < region) are 1 .. region - 1, the
+// latched states follow.  Two bytes share a class iff every state sends them
+// to the same target and, from multi-pattern states, with the same latch[]
+// value.  No skip descriptors and no literal table: every byte is walked.
+struct DenseDfa {
+  uint32_t nstates = 0;          // incl. dead; <= kDenseMaxStates
+  uint32_t ncls = 0;             // byte classes (<= 256)
+  uint8_t cmap[256] = {0};       // byte -> class
+  std::vector<uint16_t> table;   // T16[state * ncls + cls]: target state
+  std::vector<uint32_t> es;      // per state: the packed es[base] codes
+  std::vector<uint32_t> latch;   // per slot of the states < region (0xffffffff none)
+  uint32_t start_state = 0;      // 0 = dead start
+  uint32_t region = 1;           // states >= region are latched
+  uint32_t start_latch = 0xffffffffu;
+};
+constexpr uint32_t kDenseMaxStates = 65535;  // u16 targets
+
+// Derive the dense form of p (the states reachable from its start).  false:
+// more than kDenseMaxStates states -- the automaton stays packed.
+bool build_dense(const PackedDfa& p, DenseDfa* out);
+
+// Reference walk of a dense DFA on the host: packed_walk's end code.
+uint32_t dense_walk(const DenseDfa& d, const uint8_t* s, size_t n);
+
 // Explicit-transition estimate of one pattern (its literal prefix plus its
 // residual automaton), used to chunk huge pattern sets before building.
 uint64_t pattern_slot_estimate(const re::Ast& a);

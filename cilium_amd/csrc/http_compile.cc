@@ -21,6 +21,7 @@
 //      smallest matching rule index = HttpNetworkPolicyRule OR semantics
 //      (envoy/cilium_network_policy.h:98-105) with a deterministic index.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <regex>
@@ -1112,6 +1113,42 @@ CompileResult compile_http_core(const l7m_http_rule* rules, size_t n, const Poli
     fd[f].alit_lds = 1;
     fd[f].alit_pats = img_take(words);
   }
+  // Dense class-compressed form (program.h kDfaDense, l7m_opts.flags) of the
+  // packed automata that stay in the program: the fields' value automata and
+  // the forced-capture patterns' R automata, never the header-name automaton.
+  // L7M_OPT_DENSE_DFA converts a group whose u16 table is smaller than its
+  // slot table (prefix tries are smaller packed), ..._ALWAYS every group that
+  // fits u16 state ids.  The class map's copy goes to LDS while the budget
+  // lasts, as for search automata.
+  std::vector<DenseDfa> dense(ndt);
+  uint32_t n_dense = 0;
+  {
+    uint32_t dflags = opts.flags;
+    if (const char* e = std::getenv("L7M_DENSE_DFA")) dflags |= static_cast<uint32_t>(std::atoi(e)) & 3u;
+    std::vector<char> cand(ndt, 0);
+    for (uint32_t k = 0; k < ndfa; ++k) cand[k] = 1;
+    for (uint32_t k : dcap_rdfa)
+      if (k != kNone) cand[k] = 1;
+    for (uint32_t k = 0; k < ndt && !re2 && (dflags & (L7M_OPT_DENSE_DFA | L7M_OPT_DENSE_DFA_ALWAYS)); ++k) {
+      if (!cand[k] || dd[k].kind != kDfaPacked || dd[k].lds_table != kNone) continue;
+      const PackedDfa& d = *all[k].d;
+      DenseDfa dn;
+      if (!build_dense(d, &dn)) continue;
+      if (!(dflags & L7M_OPT_DENSE_DFA_ALWAYS) && 2ull * dn.table.size() >= 4ull * d.n_slots) continue;
+      dense[k] = std::move(dn);
+      const DenseDfa& D = dense[k];
+      total_states -= dd[k].nstates;
+      dd[k].kind = kDfaDense;
+      dd[k].start_base = D.start_state;
+      dd[k].region = D.region;
+      dd[k].nstates = D.nstates;
+      dd[k].n_slots = D.nstates * D.ncls;
+      dd[k].acc_ncls = D.ncls;
+      dd[k].lds_cmap = img + 64 <= budget ? img_take(64) : kNone;
+      total_states += dd[k].nstates;
+      ++n_dense;
+    }
+  }
   // ---- program layout ----
   HttpHeader h;
   std::memset(&h, 0, sizeof h);
@@ -1184,7 +1221,7 @@ CompileResult compile_http_core(const l7m_http_rule* rules, size_t n, const Poli
       slow_span[i].len /= 2;  // pairs
     }
   }
-  for (uint32_t k = 0; k < ndfa; ++k) h.search |= dd[k].kind != kDfaPacked ? 1u : 0u;
+  for (uint32_t k = 0; k < ndfa; ++k) h.search |= dd[k].kind == kDfaSearch || dd[k].kind == kDfaAlit ? 1u : 0u;
   h.ent_mask = ent_slots - 1;
   h.ent_tab_off = take(2ull * ent_slots);
   h.off_pool = take(pool.size());
@@ -1198,6 +1235,11 @@ CompileResult compile_http_core(const l7m_http_rule* rules, size_t n, const Poli
       dd[k].acc_mid_off = take(kSearchMaxMid);
     } else if (dd[k].kind == kDfaAlit) {
       dd[k].table_off = dd[k].es_off = dd[k].latch_off = take(0);
+    } else if (dd[k].kind == kDfaDense) {
+      dd[k].table_off = take((dense[k].table.size() + 1) / 2);  // u16 entries
+      dd[k].es_off = take(dense[k].es.size());
+      dd[k].latch_off = take(dense[k].latch.size());
+      dd[k].acc_cmap_off = take(256 / 4);
     } else {
       dd[k].table_off = take(all[k].d->n_slots);
       dd[k].es_off = take(all[k].d->n_slots);
@@ -1213,7 +1255,7 @@ CompileResult compile_http_core(const l7m_http_rule* rules, size_t n, const Poli
   // dependent table read per byte.
   std::vector<std::vector<uint32_t>> lit_words(ndt);
   for (uint32_t k = 0; k < ndfa; ++k) {
-    if (dd[k].lds_table != kNone || !all[k].grp) continue;
+    if (dd[k].lds_table != kNone || !all[k].grp || dd[k].kind == kDfaDense) continue;  // (dense: every byte is walked)
     const Group& g = *all[k].grp;
     bool any = false;
     for (uint32_t l = 0; l < g.pats.size(); ++l) {
@@ -1266,6 +1308,13 @@ CompileResult compile_http_core(const l7m_http_rule* rules, size_t n, const Poli
       if (dd[k].lds_search != kNone) std::memcpy(I + dd[k].lds_search, sd.table.data(), sd.table.size() * 4ull);
       if (dd[k].lds_mid != kNone) std::memcpy(I + dd[k].lds_mid, sd.midmask.data(), sd.midmask.size() * 4ull);
       std::memcpy(P + dd[k].acc_mid_off, sd.midmask.data(), sd.midmask.size() * 4ull);
+    } else if (dd[k].kind == kDfaDense) {
+      const DenseDfa& D = dense[k];
+      std::memcpy(P + dd[k].table_off, D.table.data(), D.table.size() * 2ull);
+      std::memcpy(P + dd[k].es_off, D.es.data(), D.es.size() * 4ull);
+      std::memcpy(P + dd[k].latch_off, D.latch.data(), D.latch.size() * 4ull);
+      std::memcpy(P + dd[k].acc_cmap_off, D.cmap, 256);
+      if (dd[k].lds_cmap != kNone) std::memcpy(I + dd[k].lds_cmap, D.cmap, 256);
     } else {
       std::memcpy(P + dd[k].table_off, d.table.data(), d.n_slots * 4ull);
       std::memcpy(P + dd[k].es_off, d.es.data(), d.n_slots * 4ull);
@@ -1413,6 +1462,7 @@ CompileResult compile_http_core(const l7m_http_rule* rules, size_t n, const Poli
   res.info.total_dfa_states = total_states;
   res.info.program_bytes = static_cast<uint64_t>(w) * 4;
   res.info.n_counters = static_cast<uint32_t>(n) + 2;
+  res.info.n_dense_dfas = n_dense;
   return res;
 }
 

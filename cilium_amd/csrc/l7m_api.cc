@@ -233,6 +233,7 @@ int launch(const l7m_ruleset* crs, const void* arena, size_t arena_bytes, const 
     const DfaDesc* dd = reinterpret_cast<const DfaDesc*>(rs->program.data() + h.off_dfas);
     for (uint32_t k = 0; k < h.n_dfas; ++k)
       if (dd[k].lit_tab != kNone) flags |= kLaunchLiterals;
+    if (rs->info.n_dense_dfas) flags |= kLaunchDense;  // (value and forced-capture R automata)
     e = launch_http(dprog, h, static_cast<const uint8_t*>(arena), arena_bytes, static_cast<const uint64_t*>(offs),
                     n, static_cast<int32_t*>(verdicts), static_cast<unsigned long long*>(hits),
                     stream, cus, flags, done);

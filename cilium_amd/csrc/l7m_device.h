@@ -87,6 +87,9 @@ uint32_t http_stage_bytes(const HttpHeader& h);
 // literal tables (DfaDesc::lit_tab), so the kernel instantiation that uses
 // them is launched.
 constexpr uint32_t kLaunchLiterals = 1u << 29;  // L7M_FLAG_DIAG_* use bits 30, 31
+// ... the program has dense automata (program.h kDfaDense): the instantiation
+// that walks them (l7m_http_impl.h kFeatDense)
+constexpr uint32_t kLaunchDense = 1u << 28;
 // Completion signal of a first-pass launch (the batcher's latency path):
 // every wave, once its verdicts are visible system-wide, adds one to *ctr
 // (device memory, zero between launches); the last one resets it and stores

@@ -1,8 +1,9 @@
 // l7m_http_impl.h -- device code of the HTTP verdict kernels (design:
 // l7m_kernels.hip).  Included by l7m_kernels.hip (search-dialect and
 // diagnostic instantiations, the launcher) and by l7m_http_feat.hip, which
-// instantiates the ECMAScript first-pass and slow-pass kernels of ONE
-// feature set (kFeat) per translation unit, so they compile in parallel.
+// instantiates the ECMAScript first-pass and slow-pass kernels of one
+// feature set (kFeat) and its dense twin per translation unit, so they
+// compile in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -199,6 +200,48 @@ __device__ __forceinline__ uint32_t walk_hbm(const uint32_t* __restrict__ img, c
   }
 #undef L7M_STEP
   return end_code<false>(img, prog, dd, base, last);
+}
+
+// Dense class-compressed automaton (program.h kDfaDense, dfa_pack.h DenseDfa),
+// walked from the program: per byte the class map (its LDS copy when kLdsMap,
+// else the program's; independent of the state, so off the dependent chain),
+// a 24-bit multiply-add (state < 2^16, classes <= 256: full rate, a 32-bit
+// multiply is quarter rate) and ONE dependent 2-byte read of the u16 table.
+// State 0 is an all-zero row, so a dead walk stays dead without a check and
+// the exit test runs once per block, as in walk_hbm.  The end code is the
+// packed kind's with dense indexing: es[state], latch[slot of the last
+// transition taken from a multi-pattern state (< region)].
+template <bool kLdsMap, class Src>
+__device__ __forceinline__ uint32_t walk_dense_map(const uint32_t* __restrict__ img, const uint32_t* __restrict__ prog,
+                                                   const DfaDesc& dd, const Src& src, uint32_t pos, uint32_t len) {
+  typedef __attribute__((address_space(1))) const uint16_t* gptr_u16;
+  typedef __attribute__((address_space(1))) const uint8_t* gptr_u8;
+  typedef __attribute__((address_space(3))) const uint8_t* lptr_u8;
+  const gptr_u16 T = (gptr_u16)(prog + dd.table_off);
+  const gptr_u8 cm = (gptr_u8)(prog + dd.acc_cmap_off);
+  const uint32_t cml = 4u * dd.lds_cmap;  // image byte address (the image starts at LDS address 0)
+  const uint32_t ncls = dd.acc_ncls, region = dd.region;
+  uint32_t st = dd.start_base;
+  uint32_t last = kNone;
+#define L7M_STEP(B)                                                                               \
+  {                                                                                               \
+    const uint32_t b_ = (B);                                                                      \
+    const uint32_t c_ = kLdsMap ? *reinterpret_cast<lptr_u8>(static_cast<uintptr_t>(cml + b_)) : cm[b_]; \
+    const uint32_t slot_ = __umul24(st, ncls) + c_;                                               \
+    last = st < region ? slot_ : last;                                                            \
+    st = T[slot_];                                                                                \
+  }
+  uint32_t k = 0;
+  if (st) L7M_WALK_BYTES(L7M_STEP, !st)
+#undef L7M_STEP
+  return end_code<false>(img, prog, dd, st, last);
+}
+
+template <class Src>
+__device__ __forceinline__ uint32_t walk_dense(const uint32_t* __restrict__ img, const uint32_t* __restrict__ prog,
+                                               const DfaDesc& dd, const Src& src, uint32_t pos, uint32_t len) {
+  if (dd.lds_cmap != kNone) return walk_dense_map<true>(img, prog, dd, src, pos, len);
+  return walk_dense_map<false>(img, prog, dd, src, pos, len);
 }
 
 // A walk through an LDS slot table, re-encoded by the compiler for it
@@ -634,7 +677,7 @@ __device__ __forceinline__ uint32_t gram_select(const Ctx& c, const FieldDesc& f
   return m;
 }
 
-template <bool kLit, bool kSearch, class Src>
+template <bool kLit, bool kSearch, bool kDense, class Src>
 __device__ __forceinline__ uint32_t walk_dfa(const Ctx& c, uint32_t d, const Src& src, uint32_t pos, uint32_t len);
 template <bool kSearch>
 __device__ __forceinline__ bool code_has(const Ctx& c, uint32_t d, uint32_t code, uint32_t p);
@@ -680,7 +723,7 @@ __device__ __forceinline__ void alit_scan(const Ctx& c, const FieldDesc& fd, con
     }
     if (!eq) return;
     if (a0.z != kNone) {
-      const uint32_t rc = walk_dfa<false, false>(c, fd.resid_dfa, src, s + ln, pos + len - (s + ln));
+      const uint32_t rc = walk_dfa<false, false, false>(c, fd.resid_dfa, src, s + ln, pos + len - (s + ln));
       if (!code_has<false>(c, fd.resid_dfa, rc, a0.z)) return;
     }
     codes.orbits(a0.y >> 8, 1u << (a0.y & 31u));
@@ -750,9 +793,12 @@ __device__ __forceinline__ void alit_scan(const Ctx& c, const FieldDesc& fd, con
   }
 }
 
-template <bool kLit, bool kSearch, class Src>
+// kDense: the program has dense automata (program.h kDfaDense) among its value
+// / forced-capture R automata (the header-name and residual automata never are)
+template <bool kLit, bool kSearch, bool kDense, class Src>
 __device__ __forceinline__ uint32_t walk_dfa(const Ctx& c, uint32_t d, const Src& src, uint32_t pos, uint32_t len) {
   const DfaDesc& dd = c.dds[d];
+  if (kDense && dd.kind == kDfaDense) return walk_dense(c.img, c.prog, dd, src, pos, len);
   if (kSearch && dd.kind == kDfaSearch) return walk_search(c, dd, src, pos, len);
   if (dd.lds_table != kNone) return walk_lds(c.img, c.prog, dd, src, pos, len);
   return walk_hbm<kLit>(c.img, c.prog, dd, src, pos, len);
@@ -847,7 +893,7 @@ __device__ __forceinline__ void hprof(uint64_t (&prof)[8], int i) {
 // Forced-capture back-reference pattern (program.h DcapSpec, regex_ecma.h
 // DcapForm) on the field value [p, p + len): P1, the maximal class run, L2,
 // the run again, R's automaton over the rest -- exactly regex_match's answer.
-template <bool kLit, class Src>
+template <bool kLit, bool kDense, class Src>
 __device__ __forceinline__ bool dcap_holds(const Ctx& c, const DcapSpec& sp, const Src& src, uint32_t p, uint32_t len) {
   const uint32_t l1 = sp.lens & 0xffffu, l2 = sp.lens >> 16;
   if (len < l1 + l2) return false;
@@ -870,7 +916,7 @@ __device__ __forceinline__ bool dcap_holds(const Ctx& c, const DcapSpec& sp, con
     if (src.byte(p + e + l2 + i) != src.byte(p + l1 + i)) return false;
   const uint32_t t = e + l2 + r;
   if (sp.rdfa == kNone) return t == len;
-  const uint32_t code = walk_dfa<kLit, false>(c, sp.rdfa, src, p + t, len - t);
+  const uint32_t code = walk_dfa<kLit, false, kDense>(c, sp.rdfa, src, p + t, len - t);
   return code_has<false>(c, sp.rdfa, code, 0);
 }
 
@@ -889,9 +935,10 @@ constexpr int32_t kNeedVerify = INT32_MIN;
 // Instantiation features of the HTTP kernels (template parameter kFeat):
 // kFeatLit: the program has literal tables (DfaDesc::lit_tab) for HBM-walked
 // DFAs; kFeatDcap: it has forced-capture back-reference patterns (program.h
-// DcapSpec).  Programs without them run the plain instantiation, whose code
-// and register allocation neither feature touches.
-constexpr int kFeatLit = 1, kFeatDcap = 2;
+// DcapSpec); kFeatDense: some of its automata are dense (program.h kDfaDense).
+// Programs without them run the plain instantiation, whose code and register
+// allocation no feature touches.
+constexpr int kFeatLit = 1, kFeatDcap = 2, kFeatDense = 4;
 // First pass: the request's smallest candidate may be a slow-path rule
 // (kCrSlow): it is queued for http_slow_kernel, which decides it exactly.
 constexpr int32_t kDeferred = INT32_MIN + 1;
@@ -920,7 +967,7 @@ __device__ bool field_at(const Ctx& c, const HttpHeader& h, const Src& src, uint
     if (h.lds_name_tab != kNone) {
       g = name_field_of(c, h, src, p, nl);
     } else {
-      const uint32_t code = walk_dfa<false, false>(c, h.n_dfas, src, p, nl);
+      const uint32_t code = walk_dfa<false, false, false>(c, h.n_dfas, src, p, nl);
       if (code & kLatchedBit) g = 3u + (code & ~kLatchedBit);
       else if (code) g = c.name_field[code];
     }
@@ -943,7 +990,7 @@ template <int kReg, int kAblate, int kFeat, class Src>
 __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const HttpHeader& h, const Src& src, uint64_t limit,
                                              WalkOut<kReg>& o, uint64_t (&prof)[8]) {
   if constexpr (kProf && Src::kLds) prof[0] = __builtin_amdgcn_s_memtime();
-  constexpr bool kLit = (kFeat & kFeatLit) != 0, kDcap = (kFeat & kFeatDcap) != 0;
+  constexpr bool kLit = (kFeat & kFeatLit) != 0, kDcap = (kFeat & kFeatDcap) != 0, kDense = (kFeat & kFeatDense) != 0;
   Codes<kReg>& codes = o.codes;
   if (limit < L7M_HTTP_REC_FIXED) return L7M_VERDICT_PARSE_ERROR;
   const uint32_t w0 = src.word(0), w1 = src.word(1), w2 = src.word(2), w3 = src.word(3), w4 = src.word(4);
@@ -1039,7 +1086,7 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const HttpHeader& h, 
         if (h.lds_name_tab != kNone) {
           f = name_field_of(c, h, src, hp, nl);
         } else {
-          const uint32_t code = walk_dfa<false, false>(c, h.n_dfas, src, hp, nl);
+          const uint32_t code = walk_dfa<false, false, false>(c, h.n_dfas, src, hp, nl);
           if (code & kLatchedBit) f = 3u + (code & ~kLatchedBit);
           else if (code) f = c.name_field[code];
         }
@@ -1100,7 +1147,7 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const HttpHeader& h, 
             continue;
           }
         }
-        const uint32_t code = walk_dfa<kLit, (kReg < 0)>(c, d, src, p, len);
+        const uint32_t code = walk_dfa<kLit, (kReg < 0), kDense>(c, d, src, p, len);
         HPROF(3);  // the walk, end code included
         codes.set(d, code);
         touch(d, code);
@@ -1108,7 +1155,7 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const HttpHeader& h, 
       if constexpr (kDcap)
         for (uint32_t m = fd.dcap_mask; m; m &= m - 1) {
           const uint32_t k = static_cast<uint32_t>(__builtin_ctz(m));
-          if (dcap_holds<kLit>(c, dspec[k], src, p, len)) dcap |= 1u << k;
+          if (dcap_holds<kLit, kDense>(c, dspec[k], src, p, len)) dcap |= 1u << k;
         }
     }
   }

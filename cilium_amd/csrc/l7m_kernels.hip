@@ -40,6 +40,10 @@ L7M_FEAT_DECL(0)
 L7M_FEAT_DECL(1)
 L7M_FEAT_DECL(2)
 L7M_FEAT_DECL(3)
+L7M_FEAT_DECL(4)
+L7M_FEAT_DECL(5)
+L7M_FEAT_DECL(6)
+L7M_FEAT_DECL(7)
 #undef L7M_FEAT_DECL
 
 size_t http_lds_bytes(const HttpHeader& h, uint32_t stage) {
@@ -77,8 +81,8 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
   const dim3 grid(static_cast<uint32_t>(blocks));
   const bool reg = h.n_dfas <= kRegDfas;
   if (flags & (L7M_FLAG_DIAG_WALK_ONLY | L7M_FLAG_DIAG_COPY_ONLY)) {  // diagnostic ablations
-    // (register end codes only; no search automata, no slow-path queue)
-    if (!reg || h.search || h.n_slow) return hipErrorInvalidValue;
+    // (register end codes only; no search or dense automata, no slow-path queue)
+    if (!reg || h.search || h.n_slow || (flags & kLaunchDense)) return hipErrorInvalidValue;
     if (flags & L7M_FLAG_DIAG_COPY_ONLY)
       return launch_one<kNoHits, 8, 2>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, stage);
     return launch_one<kNoHits, 8, 1>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, stage);
@@ -149,12 +153,18 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
     vms2 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + 512 + 2 * qbytes + v1);
   }
   // the instantiation with the program's features (literal tables, forced
-  // captures), each compiled in its own translation unit (l7m_http_feat.hip)
-  const int feat = (lit ? kFeatLit : 0) | (h.lds_dcap != kNone ? kFeatDcap : 0);
-  static decltype(&launch_http_main_f0) const mains[4] = {launch_http_main_f0, launch_http_main_f1,
-                                                           launch_http_main_f2, launch_http_main_f3};
-  static decltype(&launch_http_slow_f0) const slows[4] = {launch_http_slow_f0, launch_http_slow_f1,
-                                                           launch_http_slow_f2, launch_http_slow_f3};
+  // captures, dense automata); l7m_http_feat.hip compiles one translation
+  // unit per literal / capture set, holding it and its dense twin (+ 4)
+  const int feat = (lit ? kFeatLit : 0) | (h.lds_dcap != kNone ? kFeatDcap : 0) |
+                   ((flags & kLaunchDense) ? kFeatDense : 0);
+  static decltype(&launch_http_main_f0) const mains[8] = {launch_http_main_f0, launch_http_main_f1,
+                                                           launch_http_main_f2, launch_http_main_f3,
+                                                           launch_http_main_f4, launch_http_main_f5,
+                                                           launch_http_main_f6, launch_http_main_f7};
+  static decltype(&launch_http_slow_f0) const slows[8] = {launch_http_slow_f0, launch_http_slow_f1,
+                                                           launch_http_slow_f2, launch_http_slow_f3,
+                                                           launch_http_slow_f4, launch_http_slow_f5,
+                                                           launch_http_slow_f6, launch_http_slow_f7};
   // the completion signal only where this launch decides every request
   const DoneSignal sig = done && !h.n_slow ? *done : DoneSignal{nullptr, nullptr, 0};
   hipError_t e = mains[feat](mode, R, grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, stage,

@@ -78,13 +78,14 @@ struct DfaDesc {
                          // one word per base >= skip_lim), or kNone (LDS-walked DFAs only)
   uint32_t skip_lim;     // skip rows: bases >= skip_lim (low 16 bits); the literal pool
                          // (skip_lim >> 16 words) sits right below lds_skip
-  uint32_t kind;         // kDfaPacked, or kDfaSearch (below)
-  uint32_t acc_cmap_off; // kDfaSearch: program word offset of the 256-byte byte -> class map
+  uint32_t kind;         // kDfaPacked, kDfaSearch or kDfaDense (below)
+  uint32_t acc_cmap_off; // kDfaSearch, kDfaDense: program word offset of the 256-byte byte -> class map
   uint32_t acc_mid_off;  // kDfaSearch: program: u32 pattern mask per mid-set id (256)
-  uint32_t acc_ncls;     // kDfaSearch: byte classes (row length of the dense table)
+  uint32_t acc_ncls;     // kDfaSearch, kDfaDense: byte classes (row length of the dense table)
   uint32_t lds_search;   // kDfaSearch: LDS image word offset of the dense table (small automata), or kNone
   uint32_t lds_mid;      // kDfaSearch: LDS image word offset of its mid masks, or kNone
-  uint32_t pad[2];       // 128 bytes: descriptor addresses are a shift of the DFA index
+  uint32_t lds_cmap;     // kDfaDense: LDS image word offset of the class map's copy (64 words), or kNone
+  uint32_t pad[1];       // 128 bytes: descriptor addresses are a shift of the DFA index
 };
 static_assert(sizeof(DfaDesc) == 128, "dfa desc is 32 words");
 
@@ -102,6 +103,18 @@ constexpr uint32_t kDfaPacked = 0, kDfaSearch = 1;
 // no table of its own, its code (the matched-pattern mask, as for kDfaSearch)
 // comes from the alit scan.
 constexpr uint32_t kDfaAlit = 2;
+// kDfaDense (dfa_pack.h DenseDfa, ECMAScript dialect, l7m_opts.flags
+// L7M_OPT_DENSE_DFA): a packed automaton walked from the program, stored as
+// one u16 target per (state, byte class) instead of the sparse slot table:
+//     slot = state * acc_ncls + cmap[b];  state = T16[slot]     (state 0 = dead,
+// an all-zero row).  table_off: the u16 table (n_slots = nstates * acc_ncls
+// entries, zero-padded to whole words); es_off: u32 es[nstates]; latch_off:
+// u32 latch[region * acc_ncls], indexed by the slot of the last transition
+// taken from a state < region (the multi-pattern states); start_base: the
+// start state.  End codes, sets and candidate entries are the packed kind's.
+// lds_table, lds_es, lds_latch, lds_skip and lit_tab are kNone: every byte is
+// walked, from the program.
+constexpr uint32_t kDfaDense = 3;
 constexpr uint32_t kSearchMaxPats = 32, kSearchMaxMid = 256;
 constexpr uint32_t kLdsSearchMaxWords = 2048;  // search tables up to 8 KiB are walked from LDS
 

@@ -43,6 +43,8 @@ L4_TCP, L4_UDP = 0, 1
 
 DIALECT_ENVOY_ECMA_FULL = 0
 DIALECT_RE2_SEARCH = 1
+OPT_DENSE_DFA = 1         # l7m_opts.flags: dense DFA kind where its table is the smaller one
+OPT_DENSE_DFA_ALWAYS = 2  # ... wherever it can be built (tests, experiments)
 
 FLAG_DIAG_WALK_ONLY = 0x40000000  # profiling ablations: verdicts NOT valid
 FLAG_DIAG_COPY_ONLY = 0x80000000
@@ -111,7 +113,7 @@ class _Info(ctypes.Structure):
     _fields_ = [("proto", ctypes.c_uint32), ("n_rules", ctypes.c_uint32),
                 ("n_fields", ctypes.c_uint32), ("n_dfas", ctypes.c_uint32),
                 ("total_dfa_states", ctypes.c_uint64), ("program_bytes", ctypes.c_uint64),
-                ("n_counters", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+                ("n_counters", ctypes.c_uint32), ("n_dense_dfas", ctypes.c_uint32)]
 
 
 class _Matcher(ctypes.Structure):
@@ -436,19 +438,23 @@ def get_http_rule(r: PortRuleHTTP) -> List[HeaderMatcher]:
 # --------------------------------------------------------------------------
 # Arena packing
 # --------------------------------------------------------------------------
+def _http_req_struct(q: HTTPRequest, keep: list) -> _HttpReq:
+    names = (ctypes.c_char_p * max(1, len(q.headers)))(*[_b(h[0]) for h in q.headers])
+    vals = (ctypes.c_char_p * max(1, len(q.headers)))(*[_b(h[1]) for h in q.headers])
+    keep += [names, vals]
+    return _HttpReq(_b(q.method), _b(q.path), _b(q.authority),
+                    ctypes.cast(names, ctypes.POINTER(ctypes.c_char_p)),
+                    ctypes.cast(vals, ctypes.POINTER(ctypes.c_char_p)),
+                    len(q.headers), q.remote_id, q.dport, 1 if q.ingress else 0, q.policy)
+
+
 def pack_http(reqs: Sequence[HTTPRequest]) -> Tuple[np.ndarray, np.ndarray]:
     """Pack requests into (arena uint8[], offsets uint64[]) via l7m_pack_http."""
     keep: list = []
     arr = (_HttpReq * max(1, len(reqs)))()
     total = 0
     for i, q in enumerate(reqs):
-        names = (ctypes.c_char_p * max(1, len(q.headers)))(*[_b(h[0]) for h in q.headers])
-        vals = (ctypes.c_char_p * max(1, len(q.headers)))(*[_b(h[1]) for h in q.headers])
-        keep += [names, vals]
-        arr[i] = _HttpReq(_b(q.method), _b(q.path), _b(q.authority),
-                          ctypes.cast(names, ctypes.POINTER(ctypes.c_char_p)),
-                          ctypes.cast(vals, ctypes.POINTER(ctypes.c_char_p)),
-                          len(q.headers), q.remote_id, q.dport, 1 if q.ingress else 0, q.policy)
+        arr[i] = _http_req_struct(q, keep)
         sz = _lib.l7m_http_record_size(ctypes.byref(arr[i]))
         if sz == 0:
             raise L7Error(L7M_EINVAL, f"request {i} is not encodable")
@@ -515,18 +521,22 @@ class RuleSet:
         return buf
 
     @staticmethod
-    def _opts(dialect: int, max_dfa_states: int, max_table_bytes: int, lds_budget_bytes: int = 0) -> _Opts:
-        return _Opts(ctypes.sizeof(_Opts), dialect, max_dfa_states, 0, max_table_bytes, lds_budget_bytes, 0)
+    def _opts(dialect: int, max_dfa_states: int, max_table_bytes: int, lds_budget_bytes: int = 0,
+              dense_dfa: int = 0) -> _Opts:
+        return _Opts(ctypes.sizeof(_Opts), dialect, max_dfa_states, dense_dfa, max_table_bytes, lds_budget_bytes, 0)
 
     @classmethod
     def compile_http(cls, rules: Sequence[PortRuleHTTP], dialect: int = DIALECT_ENVOY_ECMA_FULL,
                      max_dfa_states: int = 0, max_table_bytes: int = 0,
-                     lds_budget_bytes: int = 0) -> "RuleSet":
+                     lds_budget_bytes: int = 0, dense_dfa: int = 0) -> "RuleSet":
+        """dense_dfa: l7m_opts.flags -- OPT_DENSE_DFA (1) stores the automata walked from device
+        memory in the dense class-compressed form where that is the smaller table,
+        OPT_DENSE_DFA_ALWAYS (2) wherever it can be built; 0 keeps them packed."""
         keep: list = []
         arr = (_HttpRule * max(1, len(rules)))(*[_http_rule_struct(r, keep) for r in rules])
         out = ctypes.c_void_p()
         err = ctypes.create_string_buffer(1024)
-        opts = cls._opts(dialect, max_dfa_states, max_table_bytes, lds_budget_bytes)
+        opts = cls._opts(dialect, max_dfa_states, max_table_bytes, lds_budget_bytes, dense_dfa)
         rc = _lib.l7m_compile_http(arr, len(rules), ctypes.byref(opts), ctypes.byref(out), err, 1024)
         if rc != L7M_OK:
             raise L7Error(rc, err.value.decode(errors="replace"))
@@ -534,13 +544,13 @@ class RuleSet:
 
     @classmethod
     def compile_http_policies(cls, policies: Sequence[NetworkPolicy], dialect: int = DIALECT_ENVOY_ECMA_FULL,
-                              lds_budget_bytes: int = 0) -> "RuleSet":
+                              lds_budget_bytes: int = 0, dense_dfa: int = 0) -> "RuleSet":
         """A NetworkPolicyMap of NPDS NetworkPolicy resources (l7m_compile_http_policies)."""
         keep: list = []
         arr = _policies_struct(policies, keep)
         out = ctypes.c_void_p()
         err = ctypes.create_string_buffer(1024)
-        opts = cls._opts(dialect, 0, 0, lds_budget_bytes)
+        opts = cls._opts(dialect, 0, 0, lds_budget_bytes, dense_dfa)
         rc = _lib.l7m_compile_http_policies(arr, len(policies), ctypes.byref(opts), ctypes.byref(out), err, 1024)
         if rc != L7M_OK:
             raise L7Error(rc, err.value.decode(errors="replace"))
@@ -601,9 +611,10 @@ class RuleSet:
 
     # ---- evaluation -------------------------------------------------------
     def eval(self, arena: np.ndarray, offsets: np.ndarray, hits: Optional[np.ndarray] = None,
-             identities: Optional[np.ndarray] = None) -> np.ndarray:
+             identities: Optional[np.ndarray] = None, flags: int = 0) -> np.ndarray:
         """Host buffers -> int32 verdicts (H2D, kernel, D2H on the current device).
-        identities: per-request source identity (Kafka rule sets, l7m_eval_ids)."""
+        identities: per-request source identity (Kafka rule sets, l7m_eval_ids).
+        flags: 0, or FLAG_DIAG_* (profiling ablations: verdicts NOT valid)."""
         arena = np.ascontiguousarray(arena, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.shape[0]
@@ -616,10 +627,10 @@ class RuleSet:
             identities = np.ascontiguousarray(identities, dtype=np.uint32)
             assert identities.shape[0] == n
             rc = _lib.l7m_eval_ids(self._h, arena.ctypes.data, arena.nbytes, offsets.ctypes.data, n,
-                                   identities.ctypes.data, verdicts.ctypes.data, hp, 0)
+                                   identities.ctypes.data, verdicts.ctypes.data, hp, flags)
         else:
             rc = _lib.l7m_eval(self._h, arena.ctypes.data, arena.nbytes, offsets.ctypes.data, n,
-                               verdicts.ctypes.data, hp, 0)
+                               verdicts.ctypes.data, hp, flags)
         if rc != L7M_OK:
             raise L7Error(rc, "l7m_eval failed")
         return verdicts
@@ -688,6 +699,16 @@ class Batcher:
         rc = _lib.l7m_batcher_eval_from(self._h, record, len(record), src_identity, ctypes.byref(v))
         if rc != L7M_OK:
             raise L7Error(rc, "l7m_batcher_eval failed")
+        return v.value
+
+    def eval_http(self, req: HTTPRequest) -> int:
+        """l7m_batcher_eval_http: one request head, packed by the library."""
+        keep: list = []
+        st = _http_req_struct(req, keep)
+        v = ctypes.c_int32()
+        rc = _lib.l7m_batcher_eval_http(self._h, ctypes.byref(st), ctypes.byref(v))
+        if rc != L7M_OK:
+            raise L7Error(rc, "l7m_batcher_eval_http failed")
         return v.value
 
     def stats(self) -> Tuple[int, int]:

@@ -204,12 +204,25 @@ typedef struct {
   uint32_t struct_size;     /* sizeof(l7m_opts); 0 = use defaults               */
   uint32_t dialect;         /* L7M_DIALECT_*                                    */
   uint32_t max_dfa_states;  /* per DFA group before splitting (0 = default)     */
-  uint32_t flags;           /* reserved, 0                                      */
+  uint32_t flags;           /* L7M_OPT_* bits (below); 0 = defaults             */
   uint64_t max_table_bytes; /* per DFA group before splitting (0 = default)     */
   uint32_t lds_budget_bytes;/* DFA slot tables kept in LDS per workgroup
                                (0 = default 64 KiB); the rest is walked from HBM */
   uint32_t reserved;
 } l7m_opts;
+
+/* l7m_opts.flags (HTTP, ECMAScript dialect; ignored elsewhere).  An automaton
+ * too large for LDS is walked from device memory in its packed double-array
+ * form, one slot per explicit transition spread over up to 2^24 slots.  The
+ * dense kind stores the same automaton as one 16-bit target per (state, byte
+ * class): smaller when the states have many transitions (`.*`, look-ahead,
+ * \b products: 50 MB -> 4 MB for a 50 k-state :path automaton), larger for
+ * prefix tries.  Automata of more than 65,535 states, automata walked from
+ * LDS, the header-name automaton and RE2-dialect programs keep the packed
+ * form.  Verdicts and counters do not depend on the flags.  The environment
+ * variable L7M_DENSE_DFA=1 / =2, read at each compile, ORs the same bits in. */
+#define L7M_OPT_DENSE_DFA 1u        /* dense form where its table is the smaller one */
+#define L7M_OPT_DENSE_DFA_ALWAYS 2u /* dense form wherever it can be built (tests)   */
 
 typedef struct {
   uint32_t proto;           /* L7M_PROTO_*                                       */
@@ -219,7 +232,7 @@ typedef struct {
   uint64_t total_dfa_states;
   uint64_t program_bytes;   /* size of the device program blob                  */
   uint32_t n_counters;      /* length of rule_hits arrays = n_rules + 2         */
-  uint32_t reserved;
+  uint32_t n_dense_dfas;    /* HTTP: DFA groups in the dense form (L7M_OPT_DENSE_DFA) */
 } l7m_ruleset_info;
 
 /* ---- rule compilation (cold path) ---------------------------------------- */
@@ -321,8 +334,9 @@ size_t l7m_pack_http(const l7m_http_request* reqs, size_t n, uint8_t* arena, siz
 /* ---- evaluation flags ------------------------------------------------------
  * 0 for normal use.  The DIAG flags select profiling ablations of the HTTP
  * kernel whose verdicts are NOT valid (used by bench.py --diag).  HTTP
- * programs with more than 8 value automata, RE2-dialect search automata or
- * slow-path rules have no ablation build: the call returns L7M_EDEVICE. */
+ * programs with more than 8 value automata, RE2-dialect search automata,
+ * dense automata (L7M_OPT_DENSE_DFA) or slow-path rules have no ablation
+ * build: the call returns L7M_EDEVICE. */
 #define L7M_FLAG_DIAG_WALK_ONLY 0x40000000u  /* stop after the DFA walks       */
 #define L7M_FLAG_DIAG_COPY_ONLY 0x80000000u  /* stop after staging/validation  */
 
