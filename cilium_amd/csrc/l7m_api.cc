@@ -637,6 +637,22 @@ size_t l7m_pack_http(const l7m_http_request* reqs, size_t n, uint8_t* arena, siz
   return used;
 }
 
+int l7m_http_wire_decode_device(const void* d_wire, size_t wire_bytes, const void* d_head_offs, size_t n,
+                                const void* d_meta, void* d_arena, size_t cap, void* d_rec_offsets, void* d_status,
+                                void* d_arena_bytes, void* hip_stream) {
+  if (!d_arena_bytes || (n && (!d_head_offs || !d_rec_offsets || !d_status)) || (wire_bytes && !d_wire) ||
+      (cap && !d_arena))
+    return L7M_EINVAL;
+  // what l7m_eval_device asks of its arena
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return L7M_EINVAL;
+  const hipError_t e = launch_http_wire(
+      static_cast<const uint8_t*>(d_wire), wire_bytes, static_cast<const uint64_t*>(d_head_offs), n,
+      static_cast<const l7m_http_wire_meta*>(d_meta), static_cast<uint8_t*>(d_arena), cap,
+      static_cast<uint64_t*>(d_rec_offsets), static_cast<int32_t*>(d_status), static_cast<uint64_t*>(d_arena_bytes),
+      static_cast<hipStream_t>(hip_stream));
+  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+}
+
 int l7m_eval_device(const l7m_ruleset* rs, const void* d_arena, size_t arena_bytes,
                     const void* d_offsets, size_t n, void* d_verdicts, void* d_hits,
                     void* hip_stream, uint32_t flags) {

@@ -46,12 +46,16 @@
 
 #include "../../include/l7match.h"
 #include "l7m_device.h"
+#include "l7m_http_wire.h"
 
 namespace l7m {
 bool resident_program(l7m_ruleset* rs, const uint32_t** dprog, int* kind, uint32_t* stage, uint64_t* serial);
 int eval_device_signal(const l7m_ruleset* rs, const void* d_arena, size_t arena_bytes, const void* d_offs, size_t n,
                        void* d_verdicts, hipStream_t stream, const DoneSignal& sig, bool* signalled);
 void resident_running(int dev, int delta);  // persistent grids leave those CUs out (l7m_api.cc)
+// one request head: measure, then write its record (http_wire.cc)
+void http_wire_scan_host(const uint8_t* head, size_t len, WireInfo* info);
+void http_wire_emit_host(const uint8_t* head, const WireInfo& info, const l7m_http_wire_meta* meta, uint8_t* dst);
 }
 
 namespace {
@@ -635,6 +639,15 @@ struct l7m_batcher {
   }
 
   int eval(const uint8_t* rec, size_t len, uint32_t src_identity, int32_t* verdict) {
+    return eval_fill(len, src_identity, verdict, [&](uint8_t* dst) {
+      if (len) std::memcpy(dst, rec, len);
+    });
+  }
+
+  // One request whose record of `len` bytes fill(dst) writes in place, into
+  // the batch slot reserved for it.
+  template <class Fill>
+  int eval_fill(size_t len, uint32_t src_identity, int32_t* verdict, Fill&& fill) {
     if (stop.load()) return L7M_EINVAL;
     callers.fetch_add(1);
     if (stop.load()) {
@@ -643,7 +656,9 @@ struct l7m_batcher {
     }
     const size_t padded = (len + 3) & ~size_t(3);
     if (padded > arena_cap) {
-      const int rc = eval_alone(rec, len, src_identity, verdict);
+      std::vector<uint8_t> rec(len);
+      fill(rec.data());
+      const int rc = eval_alone(rec.data(), len, src_identity, verdict);
       callers.fetch_sub(1);
       return rc;
     }
@@ -673,7 +688,7 @@ struct l7m_batcher {
       }
     }
     if (idx == 0) b->first_ns.store(t_arrive);
-    if (len) std::memcpy(b->arena + off, rec, len);
+    fill(b->arena + off);
     if (padded != len) std::memset(b->arena + off + len, 0, padded - len);
     b->offs[idx] = off;
     b->ids[idx] = src_identity;
@@ -771,6 +786,20 @@ int l7m_batcher_eval_http(l7m_batcher* b, const l7m_http_request* req, int32_t* 
   uint64_t off = 0;
   if (l7m_pack_http(req, 1, rec.data(), rec.size(), &off) != sz) return L7M_EINVAL;
   return b->eval(rec.data(), rec.size(), 0, verdict);
+}
+
+int l7m_batcher_eval_http_wire(l7m_batcher* b, const uint8_t* head, size_t len, const l7m_http_wire_meta* meta,
+                               int32_t* verdict, int32_t* status) {
+  if (!b || (!head && len) || !verdict || !status) return L7M_EINVAL;
+  l7m::WireInfo info;
+  l7m::http_wire_scan_host(head, len, &info);
+  *status = info.status;
+  if (info.status < 0) {  // not submitted
+    *verdict = L7M_VERDICT_PARSE_ERROR;
+    return L7M_OK;
+  }
+  return b->eval_fill(l7m::wire_padded(info.rec_len), 0, verdict,
+                      [&](uint8_t* dst) { l7m::http_wire_emit_host(head, info, meta, dst); });
 }
 
 int l7m_batcher_stats(l7m_batcher* b, uint64_t* batches, uint64_t* requests) {

@@ -11,6 +11,7 @@
 #include <set>
 #include <utility>
 
+#include "../../include/l7match.h"
 #include "program.h"
 
 namespace l7m {
@@ -105,6 +106,14 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
                        uint64_t arena_bytes, const uint64_t* offs, uint64_t n, int32_t* verdicts,
                        unsigned long long* hits, hipStream_t stream, int num_cus, uint32_t flags,
                        const DoneSignal* done = nullptr);
+
+// HTTP/1.x request heads -> request arena (l7m_http_wire.hip): measure pass,
+// scan and emit pass enqueued on `stream`; scratch from scratch_alloc_async.
+// *total (u64) receives the arena bytes; nothing of `arena` is written when
+// that exceeds cap.
+hipError_t launch_http_wire(const uint8_t* wire, uint64_t wire_bytes, const uint64_t* head_offs, uint64_t n,
+                            const l7m_http_wire_meta* meta, uint8_t* arena, uint64_t cap, uint64_t* rec_offsets,
+                            int32_t* status, uint64_t* total, hipStream_t stream);
 
 // Mailbox of a resident evaluator (l7m_kafka.hip kafka_resident_kernel),
 // in pinned, device-mapped host memory.  The host fills slot seq %

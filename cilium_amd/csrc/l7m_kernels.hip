@@ -180,3 +180,6 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
 }
 
 }  // namespace l7m
+
+// The HTTP/1.x wire decoder's kernels and launch_http_wire: same code object.
+#include "l7m_http_wire.hip"

@@ -53,6 +53,8 @@ PROTO_HTTP = 1
 PROTO_KAFKA = 2
 
 HTTP_REC_FIXED = 20
+# status of a request head the wire decoder refuses (L7M_WIRE_E*)
+WIRE_EINCOMPLETE, WIRE_EBADLINE, WIRE_EBADHEADER, WIRE_EDUPHOST, WIRE_ETOOMANY, WIRE_ETOOLONG = -1, -2, -3, -4, -5, -6
 F_METHOD, F_PATH, F_AUTHORITY, F_INGRESS = 1, 2, 4, 8
 
 # Every symbol include/l7match.h declares (checked by
@@ -71,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "l7m_kafka_api_key_name", "l7m_batcher_get_profile",
     "l7m_multi_create", "l7m_multi_destroy", "l7m_multi_uses_rccl", "l7m_shard_bounds", "l7m_multi_eval",
     "l7m_multi_eval_device",
+    "l7m_http_wire_arena_bound", "l7m_http_wire_decode", "l7m_http_wire_decode_device", "l7m_http_wire_encode",
+    "l7m_batcher_eval_http_wire",
 )
 
 
@@ -144,6 +148,16 @@ class _PortPolicy(ctypes.Structure):
 class _NetworkPolicy(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("ingress", ctypes.POINTER(_PortPolicy)), ("n_ingress", ctypes.c_size_t),
                 ("egress", ctypes.POINTER(_PortPolicy)), ("n_egress", ctypes.c_size_t)]
+
+
+class _WireMeta(ctypes.Structure):
+    _fields_ = [("remote_id", ctypes.c_uint32), ("dport", ctypes.c_uint16), ("policy", ctypes.c_uint16),
+                ("ingress", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
+
+
+# l7m_http_wire_meta as a numpy record (12 bytes), for decode_http_wire(meta=...)
+WIRE_META_DTYPE = np.dtype([("remote_id", "<u4"), ("dport", "<u2"), ("policy", "<u2"), ("ingress", "u1"),
+                            ("reserved", "u1", (3,))])
 
 
 class _BatcherProfile(ctypes.Structure):
@@ -277,6 +291,14 @@ def _load() -> ctypes.CDLL:
     lib.l7m_shard_bounds.argtypes = [P, sz, sz, ctypes.c_uint32, P]
     lib.l7m_multi_eval.argtypes = [P, P, P, sz, P, sz, P, P, P, ctypes.c_uint32]
     lib.l7m_multi_eval_device.argtypes = [P, P, P, P, ctypes.c_uint32]
+    lib.l7m_http_wire_arena_bound.argtypes = [sz, sz]
+    lib.l7m_http_wire_arena_bound.restype = sz
+    lib.l7m_http_wire_decode.argtypes = [P, sz, P, sz, P, P, sz, P, P, ctypes.POINTER(sz)]
+    lib.l7m_http_wire_decode_device.argtypes = [P, sz, P, sz, P, P, sz, P, P, P, P]
+    lib.l7m_http_wire_encode.argtypes = [P, sz, P, sz, P, sz, P, P]
+    lib.l7m_http_wire_encode.restype = ctypes.c_int64
+    lib.l7m_batcher_eval_http_wire.argtypes = [P, ctypes.c_char_p, sz, ctypes.POINTER(_WireMeta),
+                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     return lib
 
 
@@ -480,6 +502,97 @@ def pack_records(records: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
         o = int(offs[i])
         arena[o:o + len(r)] = np.frombuffer(r, dtype=np.uint8)
     return arena, offs
+
+
+# --------------------------------------------------------------------------
+# HTTP/1.x request heads as received (the wire path)
+# --------------------------------------------------------------------------
+def http_wire_arena_bound(wire_bytes: int, n: int) -> int:
+    """l7m_http_wire_arena_bound: arena bytes that are enough for any n heads in wire_bytes."""
+    return int(_lib.l7m_http_wire_arena_bound(wire_bytes, n))
+
+
+def join_heads(heads: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
+    """Request heads back to back: (wire uint8[], head_offs uint64[n + 1])."""
+    offs = np.zeros(len(heads) + 1, dtype=np.uint64)
+    if heads:
+        offs[1:] = np.cumsum([len(h) for h in heads], dtype=np.uint64)
+    wire = np.frombuffer(b"".join(heads), dtype=np.uint8)
+    return wire, offs
+
+
+def _wire_meta(meta, n: int) -> Optional[np.ndarray]:
+    if meta is None:
+        return None
+    meta = np.ascontiguousarray(meta, dtype=WIRE_META_DTYPE)
+    assert meta.shape[0] == n
+    return meta
+
+
+def decode_http_wire(heads, meta=None, cap: Optional[int] = None):
+    """l7m_http_wire_decode (host): heads is a sequence of bytes objects or a
+    (wire, head_offs) pair; meta None or a WIRE_META_DTYPE array.  Returns
+    (arena, offsets, status); status[i] >= 0 is the bytes of head i consumed,
+    < 0 a WIRE_E* code (its record is then the 20-byte one l7m_eval answers
+    with VERDICT_PARSE_ERROR).  cap: arena capacity (default: the bound); a
+    smaller one raises L7Error(L7M_ENOMEM) with .needed set."""
+    if isinstance(heads, tuple) and len(heads) == 2 and isinstance(heads[1], np.ndarray):
+        wire, hoffs = heads
+    else:
+        wire, hoffs = join_heads(list(heads))
+    wire = np.ascontiguousarray(wire, dtype=np.uint8)
+    hoffs = np.ascontiguousarray(hoffs, dtype=np.uint64)
+    n = hoffs.shape[0] - 1
+    meta = _wire_meta(meta, n)
+    if cap is None:
+        cap = http_wire_arena_bound(wire.nbytes, n)
+    arena = np.zeros(max(4, cap), dtype=np.uint8)
+    offs = np.zeros(n, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.int32)
+    used = ctypes.c_size_t(0)
+    rc = _lib.l7m_http_wire_decode(wire.ctypes.data, wire.nbytes, hoffs.ctypes.data, n,
+                                   None if meta is None else meta.ctypes.data, arena.ctypes.data, cap,
+                                   offs.ctypes.data, status.ctypes.data, ctypes.byref(used))
+    if rc != L7M_OK:
+        e = L7Error(rc, "l7m_http_wire_decode failed")
+        e.needed = used.value
+        raise e
+    return arena[:max(4, used.value)], offs, status
+
+
+def encode_http_wire(arena: np.ndarray, offsets: np.ndarray):
+    """l7m_http_wire_encode: records -> (wire, head_offs, status); a record the
+    grammar cannot carry gets a negative status and an empty head."""
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = offsets.shape[0]
+    hoffs = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.int32)
+    need = _lib.l7m_http_wire_encode(arena.ctypes.data, arena.nbytes, offsets.ctypes.data, n, None, 0,
+                                     hoffs.ctypes.data, status.ctypes.data)
+    if need < 0:
+        raise L7Error(int(need), "l7m_http_wire_encode failed")
+    wire = np.zeros(max(1, need), dtype=np.uint8)
+    got = _lib.l7m_http_wire_encode(arena.ctypes.data, arena.nbytes, offsets.ctypes.data, n, wire.ctypes.data, need,
+                                    hoffs.ctypes.data, status.ctypes.data)
+    if got != need:
+        raise L7Error(L7M_EINVAL, "l7m_http_wire_encode size changed")
+    return wire[:need], hoffs, status
+
+
+def decode_http_wire_device(d_wire, wire_bytes: int, d_head_offs, n: int, d_meta, d_arena, cap: int, d_offsets,
+                            d_status, d_total, stream=None) -> None:
+    """l7m_http_wire_decode_device: device pointers (ints or torch tensors) ->
+    enqueue on `stream` (int handle), no synchronisation.  d_total: one uint64;
+    when it ends up above cap, d_arena was not written."""
+    def ptr(x):
+        if x is None:
+            return None
+        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+    rc = _lib.l7m_http_wire_decode_device(ptr(d_wire), wire_bytes, ptr(d_head_offs), n, ptr(d_meta), ptr(d_arena),
+                                          cap, ptr(d_offsets), ptr(d_status), ptr(d_total), stream)
+    if rc != L7M_OK:
+        raise L7Error(rc, "l7m_http_wire_decode_device failed")
 
 
 # --------------------------------------------------------------------------
@@ -710,6 +823,18 @@ class Batcher:
         if rc != L7M_OK:
             raise L7Error(rc, "l7m_batcher_eval_http failed")
         return v.value
+
+    def eval_http_wire(self, head: bytes, remote_id: int = 0, dport: int = 0, ingress: bool = True,
+                       policy: int = 0) -> Tuple[int, int]:
+        """l7m_batcher_eval_http_wire: one request head as received -> (verdict,
+        status); a head the grammar refuses (status < 0) is not submitted."""
+        m = _WireMeta(remote_id, dport, policy, 1 if ingress else 0)
+        v, st = ctypes.c_int32(), ctypes.c_int32()
+        rc = _lib.l7m_batcher_eval_http_wire(self._h, head, len(head), ctypes.byref(m), ctypes.byref(v),
+                                             ctypes.byref(st))
+        if rc != L7M_OK:
+            raise L7Error(rc, "l7m_batcher_eval_http_wire failed")
+        return v.value, st.value
 
     def stats(self) -> Tuple[int, int]:
         b, r = ctypes.c_uint64(), ctypes.c_uint64()

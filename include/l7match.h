@@ -331,8 +331,92 @@ size_t l7m_http_record_size(const l7m_http_request* req);
 size_t l7m_pack_http(const l7m_http_request* reqs, size_t n, uint8_t* arena, size_t cap,
                      uint64_t* offsets);
 
+/* ---- HTTP/1.x request heads as received (DESIGN.md "HTTP/1.x wire decode") --
+ * The HTTP twin of the Kafka wire path: the caller holds request heads as
+ * bytes off a socket or out of a capture, back to back in `wire`; head i is
+ * wire[head_offs[i], head_offs[i+1]) (n + 1 ascending offsets, the last
+ * <= wire_bytes).  Decoding turns them into the request arena above.
+ *
+ * Grammar (strict RFC 7230): `method SP target SP HTTP/1.0|HTTP/1.1 CRLF`,
+ * then `name ":" OWS value OWS CRLF` lines, then an empty line; bytes of the
+ * slice after it are ignored.  method and name are 1+ tchar (names are lower-
+ * cased in the record); target is 1+ bytes above 0x20 other than 0x7f, copied
+ * verbatim into :path; a value holds any byte but CR, LF and NUL, OWS (SP /
+ * HTAB) stripped at both ends.  The first `host` header becomes :authority and
+ * is not a regular header; the other headers keep wire order.
+ *
+ * status[i] >= 0: bytes of the head consumed, the empty line included.
+ * status[i] < 0: an L7M_WIRE_E* code; the head still gets a record, of
+ * L7M_HTTP_REC_FIXED bytes: remote_id, dport, the ingress flag and policy
+ * from its metadata, everything else zero (rec_len too), which l7m_eval
+ * answers with L7M_VERDICT_PARSE_ERROR.  The first offending byte from the
+ * left decides the code. */
+#define L7M_WIRE_EINCOMPLETE (-1) /* the slice ends before the empty line                     */
+#define L7M_WIRE_EBADLINE (-2)    /* request line: bad method / target / version / line end   */
+#define L7M_WIRE_EBADHEADER (-3)  /* header line: bad name, obs-fold, bare LF, CR without LF,
+                                     NUL in a value                                           */
+#define L7M_WIRE_EDUPHOST (-4)    /* a second host header                                     */
+#define L7M_WIRE_ETOOMANY (-5)    /* more than 255 regular headers                            */
+#define L7M_WIRE_ETOOLONG (-6)    /* a method, target, name or value above 65535 bytes (or a
+                                     head above 2^31 - 1)                                     */
+
+typedef struct {
+  uint32_t remote_id;
+  uint16_t dport;
+  uint16_t policy;
+  uint8_t ingress;
+  uint8_t reserved[3];
+} l7m_http_wire_meta; /* 12 bytes */
+
+/* Arena capacity that is enough for any n heads in wire_bytes bytes:
+ *   20 * n + max(0, wire_bytes + wire_bytes / 4 - 15)       (0 when n == 0).
+ * Derivation: a refused head costs 20 bytes.  An accepted head of W bytes
+ * with h regular headers spends 14 wire bytes the record does not hold (two
+ * SP, the 8-byte version, two CRLF) against the record's 20 fixed bytes, and
+ * a header line spends at least `":" CRLF` (3 bytes) where the record spends
+ * a 4-byte directory entry; OWS and a host line only make the record smaller.
+ * So its record is at most W + 6 + h bytes, W + 9 + h padded, and since a
+ * line has a name, h <= (W - 16) / 4: at most W + W / 4 + 5, that is
+ * 20 + (W + W / 4 - 15).  g(W) = max(0, W + W / 4 - 15) is superadditive, so
+ * the sum over the heads is at most g(wire_bytes).  The bound is met by one
+ * head `G / HTTP/1.1 CRLF a: CRLF a: CRLF a: CRLF CRLF` (28 bytes -> 40)
+ * beside n - 1 empty slices.  A device arena additionally needs the
+ * evaluator's readable slack: allocate round_up(bound, 16). */
+size_t l7m_http_wire_arena_bound(size_t wire_bytes, size_t n);
+/* Host decoder (no device needed), and the definition the device decoder
+ * reproduces byte for byte.  meta: one entry per head, or NULL for zeros with
+ * the ingress flag set.  Writes rec_offsets[n], status[n] and *arena_bytes,
+ * the bytes the records need; pad bytes are zero.  L7M_ENOMEM when that is
+ * more than cap (*arena_bytes, rec_offsets and status are still complete; the
+ * arena then holds only the records that fit entirely); L7M_EINVAL for
+ * offsets that do not ascend or pass wire_bytes. */
+int l7m_http_wire_decode(const uint8_t* wire, size_t wire_bytes, const uint64_t* head_offs /* n+1 */,
+                         size_t n, const l7m_http_wire_meta* meta /* NULL: zeros, ingress */,
+                         uint8_t* arena, size_t cap, uint64_t* rec_offsets, int32_t* status,
+                         size_t* arena_bytes);
+/* The same on device buffers, enqueued on hip_stream (NULL = default stream)
+ * without synchronising: a measure pass, a scan and an emit pass.  d_arena
+ * must be 16-byte aligned; the output is what l7m_eval_device takes on the
+ * same stream (d_arena readable up to round_up(total, 16)).  *d_arena_bytes
+ * (u64) receives the total; when it exceeds cap no byte of d_arena is written
+ * while offsets, status and the total are still produced.  Offsets that do not
+ * ascend decode to unspecified records, without reading outside d_wire. */
+int l7m_http_wire_decode_device(const void* d_wire, size_t wire_bytes, const void* d_head_offs, size_t n,
+                                const void* d_meta, void* d_arena, size_t cap, void* d_rec_offsets,
+                                void* d_status, void* d_arena_bytes /* u64 */, void* hip_stream);
+/* The inverse (host only): `method SP path SP HTTP/1.1 CRLF`, `host:
+ * <authority>` when the record has one, the regular headers as `name: value`,
+ * the empty line.  status[i] = the head's size, or a negative code and an
+ * empty head for a record the grammar cannot carry (L7M_WIRE_EBADLINE: method
+ * or path; L7M_WIRE_EBADHEADER: a name, a value with OWS at an end or CR / LF /
+ * NUL, a record that does not parse or lacks method or path;
+ * L7M_WIRE_EDUPHOST: a regular header named host).  Returns the wire bytes
+ * (wire == NULL: the size needed; L7M_ENOMEM when cap is too small). */
+int64_t l7m_http_wire_encode(const uint8_t* arena, size_t arena_bytes, const uint64_t* rec_offsets, size_t n,
+                             uint8_t* wire, size_t cap, uint64_t* head_offs /* n+1 */, int32_t* status);
+
 /* ---- evaluation flags ------------------------------------------------------
- * 0 for normal use.  The DIAG flags select profiling ablations of the HTTP
+ * 0 for normal use. The DIAG flags select profiling ablations of the HTTP
  * kernel whose verdicts are NOT valid (used by bench.py --diag).  HTTP
  * programs with more than 8 value automata, RE2-dialect search automata,
  * dense automata (L7M_OPT_DENSE_DFA) or slow-path rules have no ablation
@@ -458,6 +542,12 @@ int l7m_batcher_eval(l7m_batcher* b, const uint8_t* record, size_t len, int32_t*
 int l7m_batcher_eval_from(l7m_batcher* b, const uint8_t* record, size_t len, uint32_t src_identity,
                           int32_t* verdict);
 int l7m_batcher_eval_http(l7m_batcher* b, const l7m_http_request* req, int32_t* verdict);
+/* One request head as received (l7m_http_wire_decode's grammar), decoded on
+ * the calling thread into the batch.  *status as there; a refused head is not
+ * submitted: *verdict = L7M_VERDICT_PARSE_ERROR and the call returns L7M_OK.
+ * meta NULL: zeros, ingress. */
+int l7m_batcher_eval_http_wire(l7m_batcher* b, const uint8_t* head, size_t len,
+                               const l7m_http_wire_meta* meta, int32_t* verdict, int32_t* status);
 int l7m_batcher_stats(l7m_batcher* b, uint64_t* batches, uint64_t* requests);
 /* Where a batch's time goes (means since creation): fill = first request
  * appended -> batch closed by a flusher; launch = closed -> kernels enqueued
