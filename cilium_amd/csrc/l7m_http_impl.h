@@ -1825,10 +1825,23 @@ __global__ __launch_bounds__(kSlowBlock) void http_slow_kernel(const uint32_t* _
       const uint32_t rlen = inb ? ((rw[0] + 3u) & ~3u) : 0u;
       if (inb && rlen <= kSlowRec - 32 && o + rlen <= arena_bytes) {
         // the record into this lane's LDS slot (16-byte loads; the slack past
-        // it is zero so over-reads see no stale bytes)
+        // it is zero so over-reads see no stale bytes).  The record starts at
+        // a 4-byte boundary, so a 16-byte load of its last 4-12 bytes could
+        // end past round_up(arena_bytes, 16), all l7m_eval_device's caller
+        // promises to be readable: those words are loaded one by one.
         const uint4* g = reinterpret_cast<const uint4*>(rw);
         uint4* l = reinterpret_cast<uint4*>(slot);
-        for (uint32_t i = 0; i < (rlen + 15) / 16 + 1; ++i) l[i] = 16 * i < rlen ? g[i] : uint4{0, 0, 0, 0};
+        for (uint32_t i = 0; i < (rlen + 15) / 16 + 1; ++i) {
+          uint4 q{0, 0, 0, 0};
+          if (16 * i + 16 <= rlen) {
+            q = g[i];
+          } else if (16 * i < rlen) {
+            q.x = rw[4 * i];
+            if (16 * i + 4 < rlen) q.y = rw[4 * i + 1];
+            if (16 * i + 8 < rlen) q.z = rw[4 * i + 2];
+          }
+          l[i] = q;
+        }
         const LdsSrc src{slot};
         v = eval_walk<kReg, 0, kFeat>(c, h, src, rlen, wo, prof);
         if (v == kNeedVerify) v = eval_verify<kReg, kTier, (kFeat & kFeatDcap) != 0>(c, h, wo, &src, vm);
