@@ -4,6 +4,7 @@
 // (the same set for programs with dense automata).  Compiled once per
 // L7M_FEAT (Makefile: build/l7m_http_f<F>.o), so the instantiations build in
 // parallel; l7m_kernels.hip launch_http picks the set a program needs.
+#include "l7m_dispatch.h"
 #include "l7m_http_impl.h"
 
 #if !defined(L7M_FEAT) || !defined(L7M_FEAT_DENSE)
@@ -16,18 +17,41 @@ namespace l7m {
 
 static_assert(L7M_FEAT_DENSE == (L7M_FEAT | kFeatDense) && L7M_FEAT < kFeatDense, "feature set numbering");
 
-#define L7M_ONE(M, RR, F)                                                                              \
-  return launch_one<M, RR, 0, F>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, \
-                                 stage, nullptr, slowq, done, hslice)
-#define L7M_MODES(RR, F)                            \
-  {                                                 \
-    if (mode == kNoHits) L7M_ONE(kNoHits, RR, F);   \
-    if (mode == kLdsHits) L7M_ONE(kLdsHits, RR, F); \
-    L7M_ONE(kGlobalHits, RR, F);                    \
-  }
-#define L7M_SLOW(RR, T, F)                                                                                \
-  return launch_slow<RR, F, T>(h, blocks, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, slowq, \
-                               slowq2, vmscratch, work)
+namespace {
+
+// First pass of feature set F: hit mode x end-code registers R (4, 8, 0 = LDS
+// columns).  Any other mode counts in global memory, any other R uses columns.
+template <int F>
+hipError_t http_main(int mode, int R, dim3 grid, size_t lds, hipStream_t stream, const uint32_t* dprog,
+                     const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n, int32_t* verdicts,
+                     unsigned long long* hits, uint32_t stage, uint32_t* slowq, DoneSignal done) {
+  mode = mode == kNoHits || mode == kLdsHits ? mode : kGlobalHits;
+  R = R == 4 || R == 8 ? R : 0;
+  return dispatch_values<int, kNoHits, kLdsHits, kGlobalHits>(mode, hipErrorInvalidValue, [&](auto M) {
+    return dispatch_values<int, 4, 8, 0>(R, hipErrorInvalidValue, [&](auto RR) {
+      return launch_one<decltype(M)::value, decltype(RR)::value, 0, F>(
+          grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, stage, nullptr, slowq, done);
+    });
+  });
+}
+
+// Slow pass of feature set F: R x tier (any tier but 1 is the second).
+template <int F>
+hipError_t http_slow(int R, int tier, const HttpHeader& h, uint32_t blocks, hipStream_t stream, const uint32_t* dprog,
+                     const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n, int32_t* verdicts,
+                     unsigned long long* hits, const uint32_t* slowq, uint32_t* slowq2, uint32_t* vmscratch,
+                     uint32_t* work) {
+  R = R == 4 || R == 8 ? R : 0;
+  tier = tier == 1 ? 1 : 2;
+  return dispatch_values<int, 4, 8, 0>(R, hipErrorInvalidValue, [&](auto RR) {
+    return dispatch_values<int, 1, 2>(tier, hipErrorInvalidValue, [&](auto T) {
+      return launch_slow<decltype(RR)::value, F, decltype(T)::value>(h, blocks, stream, dprog, arena, arena_bytes, offs,
+                                                                     n, verdicts, hits, slowq, slowq2, vmscratch, work);
+    });
+  });
+}
+
+}  // namespace
 
 // The two launch entry points of feature set F.
 #define L7M_FEAT_DEFS(F)                                                                                         \
@@ -35,32 +59,22 @@ static_assert(L7M_FEAT_DENSE == (L7M_FEAT | kFeatDense) && L7M_FEAT < kFeatDense
                                             const uint32_t* dprog, const uint8_t* arena, uint64_t arena_bytes,  \
                                             const uint64_t* offs, uint64_t n, int32_t* verdicts,                \
                                             unsigned long long* hits, uint32_t stage, uint32_t* slowq,          \
-                                            DoneSignal done, uint32_t* hslice) {                                 \
-    if (R == 4) L7M_MODES(4, F)                                                                                  \
-    if (R == 8) L7M_MODES(8, F)                                                                                  \
-    L7M_MODES(0, F)                                                                                              \
+                                            DoneSignal done) {                                                   \
+    return http_main<F>(mode, R, grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, stage,  \
+                        slowq, done);                                                                            \
   }                                                                                                              \
   hipError_t L7M_CAT(launch_http_slow_f, F)(int R, int tier, const HttpHeader& h, uint32_t blocks,              \
                                             hipStream_t stream, const uint32_t* dprog, const uint8_t* arena,    \
                                             uint64_t arena_bytes, const uint64_t* offs, uint64_t n,             \
                                             int32_t* verdicts, unsigned long long* hits, const uint32_t* slowq, \
                                             uint32_t* slowq2, uint32_t* vmscratch, uint32_t* work) {            \
-    if (tier == 1) {                                                                                             \
-      if (R == 4) L7M_SLOW(4, 1, F);                                                                             \
-      if (R == 8) L7M_SLOW(8, 1, F);                                                                             \
-      L7M_SLOW(0, 1, F);                                                                                         \
-    }                                                                                                            \
-    if (R == 4) L7M_SLOW(4, 2, F);                                                                               \
-    if (R == 8) L7M_SLOW(8, 2, F);                                                                               \
-    L7M_SLOW(0, 2, F);                                                                                           \
+    return http_slow<F>(R, tier, h, blocks, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, slowq,  \
+                        slowq2, vmscratch, work);                                                                \
   }
 
 L7M_FEAT_DEFS(L7M_FEAT)
 L7M_FEAT_DEFS(L7M_FEAT_DENSE)
 
 #undef L7M_FEAT_DEFS
-#undef L7M_SLOW
-#undef L7M_MODES
-#undef L7M_ONE
 
 }  // namespace l7m

@@ -10,6 +10,7 @@
 
 #include "../../include/l7match.h"
 #include "l7m_device.h"
+#include "l7m_wave.h"
 #include "program.h"
 #include "regex_vm.h"
 
@@ -21,7 +22,6 @@ constexpr uint32_t kWaves = kHttpWaves;
 constexpr uint32_t kBlock = kHttpBlock;
 constexpr uint32_t kMaxStage = kHttpMaxStage;  // bytes of records staged per wave and tile
 constexpr uint32_t kCopyIters = (kMaxStage + 1023) / 1024;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #ifdef L7M_PROF
 constexpr bool kProf = true;  // diagnostic build: wave timeline printed by two waves
 #else
@@ -381,20 +381,6 @@ __device__ __forceinline__ bool set_has(const uint32_t* __restrict__ pool, Span 
   return false;
 }
 
-// Per-wave aggregated counter increment: one atomic per distinct slot.
-// Must be called by every lane of the wave.
-__device__ __forceinline__ void count_slot(unsigned long long* __restrict__ hits, uint32_t slot, bool active) {
-  uint64_t todo = __ballot(active);
-  const uint32_t lane = __lane_id();
-  while (todo) {
-    const uint32_t leader = __builtin_ctzll(todo);
-    const uint32_t key = __shfl(slot, leader);
-    const uint64_t same = __ballot(active && slot == key) & todo;
-    if (lane == leader) atomicAdd(hits + key, static_cast<unsigned long long>(__popcll(same)));
-    todo &= ~same;
-  }
-}
-
 // Per-lane DFA end codes: in registers when the program has few value DFAs
 // (static-index select chains, no scratch), else in an LDS column.
 constexpr uint32_t kRegDfas = kHttpRegDfas;
@@ -532,6 +518,19 @@ struct Ctx {
   const uint32_t* cr;          // HBM: check records
   const Span* remotes;         // HBM
 };
+__device__ __forceinline__ Ctx make_ctx(const uint32_t* prog, const uint32_t* img, const HttpHeader& h) {
+  Ctx c;
+  c.prog = prog;
+  c.img = img;
+  c.dds = reinterpret_cast<const DfaDesc*>(img + h.lds_dfas);
+  c.fields = reinterpret_cast<const FieldDesc*>(img + h.lds_fields);
+  c.name_field = img + h.lds_name_field;
+  c.sets = reinterpret_cast<const Span*>(prog + h.off_sets);
+  c.pool = prog + h.off_pool;
+  c.cr = prog + h.off_cr;
+  c.remotes = reinterpret_cast<const Span*>(prog + h.off_remotes);
+  return c;
+}
 
 // Search automaton (program.h kDfaSearch, RE2 dialect): the mask of the
 // patterns matching some substring of the field -- per byte one dependent
@@ -1406,25 +1405,6 @@ __device__ __forceinline__ int32_t eval_verify(const Ctx& c, const HttpHeader& h
   return h0 ? L7M_VERDICT_DENY : L7M_VERDICT_ALLOW_NO_L7;
 }
 
-// A wave-uniform lane's 64-bit value: v_readlane (no LDS round trip, unlike
-// the ds_bpermute of __shfl); `src` must be wave-uniform.
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t src) {
-  const uint32_t lo = __builtin_amdgcn_readlane(static_cast<uint32_t>(v), src);
-  const uint32_t hi = __builtin_amdgcn_readlane(static_cast<uint32_t>(v >> 32), src);
-  return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t src) {
-  const uint32_t lo = __shfl(static_cast<uint32_t>(v), src);
-  const uint32_t hi = __shfl(static_cast<uint32_t>(v >> 32), src);
-  return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // Per-rule hit counters: none, per-workgroup LDS counters flushed once at the
 // end (small rule sets), or wave-aggregated global atomics.
 enum HitMode { kNoHits = 0, kLdsHits = 1, kGlobalHits = 2 };
@@ -1448,17 +1428,14 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
                                                uint32_t stage, uint32_t* __restrict__ scratch,
                                                uint32_t* __restrict__ slowq, bool load_image, uint32_t part,
                                                uint32_t nparts, uint32_t wave_index, uint32_t wave_count,
-                                               DoneSignal done = DoneSignal{nullptr, nullptr, 0},
-                                               uint32_t* __restrict__ hslice = nullptr) {
+                                               DoneSignal done = DoneSignal{nullptr, nullptr, 0}) {
   extern __shared__ __align__(16) uint32_t smem[];
   const HttpHeader& h = *reinterpret_cast<const HttpHeader*>(prog);
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
   uint32_t* img = smem;
   const uint32_t n_ctr = h.n_rules + 2;
-  // hit counters (kLdsHits): LDS, or (kSliceHits) this workgroup's global slice
-  uint32_t* ctr = kSliceHits ? hslice + static_cast<uint64_t>(part) * ((n_ctr + 63u) & ~63u) : smem + h.lds_image_words;
-  uint32_t* col = (kSliceHits ? smem + h.lds_image_words : ctr) +
-                  (kHits == kLdsHits && !kSliceHits ? ((n_ctr + 3u) & ~3u) : 0u);  // LDS code columns (!kReg)
+  uint32_t* ctr = smem + h.lds_image_words;  // hit counters (kLdsHits)
+  uint32_t* col = ctr + (kHits == kLdsHits ? ((n_ctr + 3u) & ~3u) : 0u);  // LDS code columns (!kReg)
   uint8_t* stg = reinterpret_cast<uint8_t*>(col + (kReg ? 0u : h.n_dfas * kBlock)) + wv * (stage + 16u);
   // This wave's contiguous share of the batch, consumed in tiles of <= 64
   // records (wave wave_index of wave_count).  The first tile's offsets are
@@ -1466,15 +1443,16 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
   // (small batches: the offsets may sit in pinned host memory, across PCIe).
   const uint64_t gw = wave_index;
   const uint64_t nw = wave_count;
-#if L7M_SPEC_TILE
-  // (kSpecTile) a small batcher batch: wave 0 takes it whole
+  // Batcher launches (a DoneSignal, <= 64 records, the whole batch within one
+  // record stage): the first wave takes every record and requests the batch's
+  // bytes from offset 0 before the offsets have arrived, so the two PCIe round
+  // trips to the pinned batch overlap, and it alone signals completion (no
+  // per-wave counter).  Measured (profiles/r06/ab_spec_tile_r6g.jsonl, config
+  // 2, 8 callers, alternated on one box): gpu phase 17.5 -> 16.1 us, 270 ->
+  // 293 k/s; the 64 M-request launch 4.095 -> 4.065 ms.
   const bool spec = done.flag && n <= 64 && arena_bytes <= stage;
   const uint64_t start = spec ? 0 : n * gw / nw;
   const uint64_t end = spec ? (gw == 0 ? n : 0) : n * (gw + 1) / nw;
-#else
-  const uint64_t end = n * (gw + 1) / nw;
-#define start (n * gw / nw)
-#endif
   auto load_offs = [&](uint64_t cur, uint64_t* o, uint64_t* onext) {
     *o = 0;
     *onext = 0;
@@ -1485,7 +1463,6 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
   };
   uint64_t o1, n1, o2, n2;
   load_offs(start, &o1, &n1);
-#if L7M_SPEC_TILE
   if (spec && gw == 0) {
     // the batch's bytes from offset 0, before the offsets (pinned host
     // memory: both requests cross PCIe; plan() below checks the guess)
@@ -1500,29 +1477,16 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
                                          16, 0, 2);
     }
   }
-#endif
   if (load_image) {
     const uint4* g = reinterpret_cast<const uint4*>(prog + h.lds_image_off);
     uint4* l = reinterpret_cast<uint4*>(img);
     for (uint32_t i = tid; i < h.lds_image_words / 4u; i += kBlock) l[i] = g[i];
   }
   if (kHits == kLdsHits)
-    for (uint32_t i = tid; i < n_ctr; i += kBlock) {
-      if constexpr (kSliceHits) __hip_atomic_store(ctr + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      else ctr[i] = 0;
-    }
+    for (uint32_t i = tid; i < n_ctr; i += kBlock) ctr[i] = 0;
   __syncthreads();
 
-  Ctx c;
-  c.prog = prog;
-  c.img = img;
-  c.dds = reinterpret_cast<const DfaDesc*>(img + h.lds_dfas);
-  c.fields = reinterpret_cast<const FieldDesc*>(img + h.lds_fields);
-  c.name_field = img + h.lds_name_field;
-  c.sets = reinterpret_cast<const Span*>(prog + h.off_sets);
-  c.pool = prog + h.off_pool;
-  c.cr = prog + h.off_cr;
-  c.remotes = reinterpret_cast<const Span*>(prog + h.off_remotes);
+  const Ctx c = make_ctx(prog, img, h);
   uint32_t* mycol = col + tid;
   // diagnostic wave timeline per tile (kProf, s_memtime): [0] top wait,
   // [1] walks, [2] entry wait, [3] issue, [4] verify + store, [5] counters;
@@ -1604,15 +1568,10 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
     }
   };
   Tile t = plan(start, o1, n1);
-#if L7M_SPEC_TILE
   if (!(spec && t.base == 0 && t.take == t.k)) {  // (a tile at offset 0 is what the guess requested)
     if (spec) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the guessed bytes have landed first
     issue_bytes(t);
   }
-#else
-#undef start
-  issue_bytes(t);
-#endif
   load_offs(t.cur + t.take, &o2, &n2);
   while (t.cur < end) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tile's LDS-DMA pieces have landed
@@ -1668,14 +1627,13 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
       uint32_t slot = kNone;
       // allows decided without a rule (no L7 rules, no port policy) are not counted
       if (lane < take && v < L7M_VERDICT_ALLOW_NO_PORT_POLICY && v != kDeferred)
-        slot = v >= 0 ? static_cast<uint32_t>(v) + 2u : (v == L7M_VERDICT_DENY ? 0u : 1u);
+        slot = hit_slot(v);
       if (kHits == kLdsHits) {
         // denies / errors are common: one add per wave for them
         const uint64_t dm = __ballot(slot == 0u), em = __ballot(slot == 1u);
-        auto add = [&](uint32_t i, uint32_t x) {
-          if constexpr (kSliceHits) (void)__hip_atomic_fetch_add(ctr + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          else atomicAdd(ctr + i, x);
-        };
+        // (a lambda: with the three calls written out, the kLdsHits search
+        // instantiation gets another register allocation)
+        auto add = [&](uint32_t i, uint32_t x) { atomicAdd(ctr + i, x); };
         if (lane == 0 && dm) add(0, static_cast<uint32_t>(__popcll(dm)));
         if (lane == 0 && em) add(1, static_cast<uint32_t>(__popcll(em)));
         if (slot != kNone && slot >= 2u) add(slot, 1u);
@@ -1711,11 +1669,10 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
   if (kHits == kLdsHits) {
     __syncthreads();
     for (uint32_t i = tid; i < n_ctr; i += kBlock) {
-      const uint32_t x = kSliceHits ? __hip_atomic_load(ctr + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ctr[i];
+      const uint32_t x = ctr[i];
       if (x) atomicAdd(hits + i, static_cast<unsigned long long>(x));
     }
   }
-#if L7M_SPEC_TILE
   if (spec && kHits == kNoHits) {
     // wave 0 decided the whole batch: it alone signals (no counter round trip)
     if (gw == 0) {
@@ -1724,7 +1681,6 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
     }
     return;
   }
-#endif
   if (done.flag) {  // (l7m_device.h DoneSignal)
     __threadfence_system();  // this wave's verdict stores (and counters) are visible system-wide
     if (lane == 0 && atomicAdd(done.ctr, 1u) == wave_count - 1u) {
@@ -1742,10 +1698,10 @@ __global__ __launch_bounds__(kBlock) L7M_HTTP_OCC void http_eval_kernel(const ui
                                                            int32_t* __restrict__ verdicts,
                                                            unsigned long long* __restrict__ hits, uint32_t stage,
                                                            uint32_t* __restrict__ scratch, uint32_t* __restrict__ slowq,
-                                                           DoneSignal done, uint32_t* __restrict__ hslice) {
+                                                           DoneSignal done) {
   http_eval_body<kHits, kReg, kAblate, kFeat>(prog, arena, arena_bytes, offs, n, verdicts, hits, stage, scratch, slowq,
                                              true, blockIdx.x, gridDim.x, blockIdx.x * kWaves + (threadIdx.x >> 6),
-                                             gridDim.x * kWaves, done, hslice);
+                                             gridDim.x * kWaves, done);
 }
 
 // Second pass over the requests the first pass deferred (a slow-path rule may
@@ -1791,16 +1747,7 @@ __global__ __launch_bounds__(kSlowBlock) void http_slow_kernel(const uint32_t* _
     for (uint32_t i = tid; i < h.lds_image_words / 4u; i += kSlowBlock) l[i] = g[i];
   }
   __syncthreads();
-  Ctx c;
-  c.prog = prog;
-  c.img = img;
-  c.dds = reinterpret_cast<const DfaDesc*>(img + h.lds_dfas);
-  c.fields = reinterpret_cast<const FieldDesc*>(img + h.lds_fields);
-  c.name_field = img + h.lds_name_field;
-  c.sets = reinterpret_cast<const Span*>(prog + h.off_sets);
-  c.pool = prog + h.off_pool;
-  c.cr = prog + h.off_cr;
-  c.remotes = reinterpret_cast<const Span*>(prog + h.off_remotes);
+  const Ctx c = make_ctx(prog, img, h);
   uint32_t* slot = img + h.lds_image_words + (kReg ? 0u : h.n_dfas * kBlock) + tid * (kSlowRec / 4);
   const uint32_t gtid = blockIdx.x * kSlowBlock + tid;
   uint32_t* vm = vmscratch + static_cast<uint64_t>(gtid) * (kTier == 1 ? kVmScratchWords : kVmScratchWords2);
@@ -1859,7 +1806,7 @@ __global__ __launch_bounds__(kSlowBlock) void http_slow_kernel(const uint32_t* _
     }
     if (hits) {
       const bool cnt = v != kDeferred && v < L7M_VERDICT_ALLOW_NO_PORT_POLICY;
-      const uint32_t sl = v >= 0 ? static_cast<uint32_t>(v) + 2u : (v == L7M_VERDICT_DENY ? 0u : 1u);
+      const uint32_t sl = hit_slot(v);
       count_slot(hits, cnt ? sl : 0u, cnt);
     }
   }
@@ -1870,15 +1817,14 @@ template <int kHits, int kReg, int kAblate = 0, int kFeat = 0>
 hipError_t launch_one(dim3 grid, size_t lds, hipStream_t stream, const uint32_t* dprog, const uint8_t* arena,
                        uint64_t arena_bytes, const uint64_t* offs, uint64_t n, int32_t* verdicts,
                        unsigned long long* hits, uint32_t stage, uint32_t* scratch = nullptr,
-                       uint32_t* slowq = nullptr, DoneSignal done = DoneSignal{nullptr, nullptr, 0},
-                       uint32_t* hslice = nullptr) {
+                       uint32_t* slowq = nullptr, DoneSignal done = DoneSignal{nullptr, nullptr, 0}) {
   // allow > 64 KiB of dynamic LDS (gfx950: 160 KiB per CU); set per device
   // and instantiation, thread-safely (l7m_device.h)
   const hipError_t e = set_lds_attr_once(reinterpret_cast<const void*>(http_eval_kernel<kHits, kReg, kAblate, kFeat>),
                                          kHttpLdsBytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((http_eval_kernel<kHits, kReg, kAblate, kFeat>), grid, dim3(kBlock), lds, stream, dprog, arena, arena_bytes,
-                     offs, n, verdicts, hits, stage, scratch, slowq, done, hslice);
+                     offs, n, verdicts, hits, stage, scratch, slowq, done);
   return hipGetLastError();
 }
 

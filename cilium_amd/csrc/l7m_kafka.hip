@@ -31,13 +31,13 @@
 
 #include "../../include/l7match.h"
 #include "l7m_device.h"
+#include "l7m_dispatch.h"
 #include "l7m_kcodec.h"
+#include "l7m_wave.h"
 #include "program.h"
 
 namespace l7m {
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // A view of a byte range with the optiopay decoder's sticky-error semantics:
 // a short read consumes what is left (io.ReadFull) and sets err.
@@ -578,18 +578,6 @@ __device__ __forceinline__ int32_t eval_kafka(const KView& v, const Span* spans,
   return first == kNone ? L7M_VERDICT_DENY : static_cast<int32_t>(first);
 }
 
-__device__ __forceinline__ void count_slot(unsigned long long* __restrict__ hits, uint32_t slot, bool active) {
-  uint64_t todo = __ballot(active);
-  const uint32_t lane = __lane_id();
-  while (todo) {
-    const uint32_t leader = __builtin_ctzll(todo);
-    const uint32_t key = __shfl(slot, leader);
-    const uint64_t same = __ballot(active && slot == key) & todo;
-    if (lane == leader) atomicAdd(hits + key, static_cast<unsigned long long>(__popcll(same)));
-    todo &= ~same;
-  }
-}
-
 constexpr uint32_t kKWaves = 16;
 constexpr uint32_t kKBlock = 64 * kKWaves;
 constexpr uint32_t kKMaxStage = 6144;
@@ -599,17 +587,6 @@ constexpr uint32_t kKMaxLdsCounters = 16384;
 constexpr uint32_t kSpanLds = (4 * kKafkaKinds + 3) & ~3u;  // words
 constexpr uint32_t kKindOkLds = (2 * kKafkaKinds + 3) & ~3u;  // words
 constexpr uint32_t kMaxCliLdsBytes = 8192;  // client table copied to LDS up to this size
-
-__device__ __forceinline__ uint64_t shfl64(uint64_t x, uint32_t src) {
-  const uint32_t lo = __shfl(static_cast<uint32_t>(x), src);
-  const uint32_t hi = __shfl(static_cast<uint32_t>(x >> 32), src);
-  return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 enum KHitMode { kKNoHits = 0, kKLdsHits = 1, kKGlobalHits = 2 };
 
@@ -788,7 +765,7 @@ __device__ __forceinline__ void kafka_eval_body(const uint32_t* __restrict__ pro
     if constexpr (kProf) prof[4] += __builtin_amdgcn_s_memtime() - te0;
     if (kHits != kKNoHits) {
       uint32_t slot = kNone;
-      if (lane < t.take) slot = verdict >= 0 ? static_cast<uint32_t>(verdict) + 2 : (verdict == -1 ? 0u : 1u);
+      if (lane < t.take) slot = hit_slot(verdict);
       if (kHits == kKLdsHits) {
         if (slot != kNone) atomicAdd(ctr + slot, 1u);
       } else {
@@ -977,21 +954,15 @@ bool kafka_resident_ok(const KafkaHeader& h, int* kind, uint32_t* stage) {
 
 hipError_t launch_kafka_resident(ResidentBox* dbox, uint64_t first_seq, int kind, uint32_t* qhdr,
                                  hipStream_t stream) {
-#define L7M_KRES(C, G)                                                                                        \
-  {                                                                                                          \
-    const hipError_t e = set_lds_attr_once(reinterpret_cast<const void*>(kafka_resident_kernel<C, G>), kKLdsBytes); \
-    if (e != hipSuccess) return e;                                                                           \
-    hipLaunchKernelGGL((kafka_resident_kernel<C, G>), dim3(1), dim3(kKBlock), kKLdsBytes, stream, dbox, first_seq, \
-                       qhdr);                                                                                \
-    return hipGetLastError();                                                                                \
-  }
-  switch (kind & 3) {
-    case 0: L7M_KRES(false, false)
-    case 1: L7M_KRES(true, false)
-    case 2: L7M_KRES(false, true)
-    default: L7M_KRES(true, true)
-  }
-#undef L7M_KRES
+  // kind & 3 (kafka_resident_ok): bit 0 the client table in LDS, bit 1 identity groups
+  return dispatch_values<int, 0, 1, 2, 3>(kind & 3, hipErrorInvalidValue, [&](auto K) {
+    constexpr bool kC = (decltype(K)::value & 1) != 0, kG = (decltype(K)::value & 2) != 0;
+    const hipError_t e = set_lds_attr_once(reinterpret_cast<const void*>(kafka_resident_kernel<kC, kG>), kKLdsBytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((kafka_resident_kernel<kC, kG>), dim3(1), dim3(kKBlock), kKLdsBytes, stream, dbox, first_seq,
+                       qhdr);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_kafka(const uint32_t* dprog, const KafkaHeader& h, const uint8_t* arena, uint64_t arena_bytes,
@@ -1018,24 +989,15 @@ hipError_t launch_kafka(const uint32_t* dprog, const KafkaHeader& h, const uint8
       return launch_k<kKNoHits, 1>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, st, cq, ids);
     return launch_k<kKNoHits, 2>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, st, cq, ids);
   }
-#define L7M_KAFKA_LAUNCH(M, C, G) \
-  return launch_k<M, 0, C, G>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, st, cq, ids)
-#define L7M_KAFKA_LAUNCH_G(M, C)        \
-  {                                     \
-    if (groups) L7M_KAFKA_LAUNCH(M, C, true); \
-    L7M_KAFKA_LAUNCH(M, C, false);      \
-  }
   const bool groups = h.n_id_slots != 0;
-  if (cli_lds) {
-    if (mode == kKNoHits) L7M_KAFKA_LAUNCH_G(kKNoHits, true);
-    if (mode == kKLdsHits) L7M_KAFKA_LAUNCH_G(kKLdsHits, true);
-    L7M_KAFKA_LAUNCH_G(kKGlobalHits, true);
-  }
-  if (mode == kKNoHits) L7M_KAFKA_LAUNCH_G(kKNoHits, false);
-  if (mode == kKLdsHits) L7M_KAFKA_LAUNCH_G(kKLdsHits, false);
-  L7M_KAFKA_LAUNCH_G(kKGlobalHits, false);
-#undef L7M_KAFKA_LAUNCH_G
-#undef L7M_KAFKA_LAUNCH
+  return dispatch_values<int, kKNoHits, kKLdsHits, kKGlobalHits>(mode, hipErrorInvalidValue, [&](auto M) {
+    return dispatch_values<bool, false, true>(cli_lds, hipErrorInvalidValue, [&](auto C) {
+      return dispatch_values<bool, false, true>(groups, hipErrorInvalidValue, [&](auto G) {
+        return launch_k<decltype(M)::value, 0, decltype(C)::value, decltype(G)::value>(
+            grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, st, cq, ids);
+      });
+    });
+  });
 }
 
 namespace {

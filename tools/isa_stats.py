@@ -6,6 +6,7 @@ on code generation without a GPU:
 
 Prints per kernel: VGPR / SGPR / LDS / scratch from the code object metadata
 and instruction counts by class (VALU, SALU, DS, global, branches, waitcnt).
+The compile and the assembly parsing are shared with tools/isa_diff.py.
 """
 import argparse
 import os
@@ -13,57 +14,79 @@ import re
 import subprocess
 import tempfile
 
-ap = argparse.ArgumentParser()
-ap.add_argument("src")
-ap.add_argument("-k", "--kernel", default="", help="substring of the kernel symbol")
-ap.add_argument("flags", nargs="*")
-a, extra = ap.parse_known_args()
-flags = a.flags + extra
+HIPCC = "/opt/rocm/bin/hipcc"
+BASE_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-munsafe-fp-atomics"]
 
-with tempfile.TemporaryDirectory() as td:
-    asm = os.path.join(td, "k.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
-                    "-munsafe-fp-atomics", *flags, a.src, "-o", asm], check=True)
-    text = open(asm).read()
 
-funcs = {}
-cur = None
-for line in text.splitlines():
-    m = re.match(r"^(_Z\S+):\s*(;.*)?$", line)
-    if m:
-        cur = m.group(1)
-        funcs[cur] = []
-        continue
-    if cur and line.startswith("\t.end_amdhsa_kernel"):
-        cur = None
-    if cur and line.startswith("\t") and not line.startswith("\t."):
-        funcs[cur].append(line.strip())
+def compile_asm(src, out, flags=BASE_FLAGS, cwd=None):
+    """Device-side assembly of one .hip file."""
+    subprocess.run([HIPCC, *flags, "--cuda-device-only", "-S", src, "-o", out], check=True, cwd=cwd)
 
-meta = {}
-for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S):
-    body = m.group(2)
-    g = lambda k: (re.search(r"\.%s (\d+)" % k, body) or [None, "?"])[1]
-    meta[m.group(1)] = (g("amdhsa_next_free_vgpr"), g("amdhsa_next_free_sgpr"),
-                        g("amdhsa_group_segment_fixed_size"), g("amdhsa_private_segment_fixed_size"))
 
-for name, ins in funcs.items():
-    if a.kernel not in name or name not in meta:
-        continue
-    c = dict(valu=0, salu=0, ds=0, glob=0, br=0, wait=0)
-    for i in ins:
-        op = i.split()[0] if i else ""
-        if op.startswith("v_"):
-            c["valu"] += 1
-        elif op.startswith("s_waitcnt"):
-            c["wait"] += 1
-        elif op.startswith("s_cbranch") or op.startswith("s_branch"):
-            c["br"] += 1
-        elif op.startswith("s_"):
-            c["salu"] += 1
-        elif op.startswith("ds_"):
-            c["ds"] += 1
-        elif op.startswith(("global_", "buffer_", "flat_")):
-            c["glob"] += 1
-    v, s, l, p = meta[name]
-    print(f"{name[:90]}\n   vgpr {v} sgpr {s} lds {l} scratch {p} | lines {len(ins)} " +
-          " ".join(f"{k} {n}" for k, n in c.items()))
+def split_functions(text):
+    """{symbol: the lines from its label to the end of its body}, in file order."""
+    funcs, cur = {}, None
+    is_func = set(re.findall(r"^\t\.type\t(\S+),@function", text, re.M))  # (not the data symbols)
+    for line in text.splitlines():
+        m = re.match(r"^(_Z\S+):\s*(;.*)?$", line)
+        if m and m.group(1) in is_func:
+            cur = funcs[m.group(1)] = []
+            continue
+        if cur is not None and (line.startswith(".Lfunc_end") or line.startswith("\t.end_amdhsa_kernel")):
+            cur = None
+        if cur is not None:
+            cur.append(line)
+    return funcs
+
+
+def kernel_descriptors(text):
+    """{kernel symbol: the lines of its .amdhsa_kernel block}."""
+    return {m.group(1): m.group(2).strip("\n").splitlines()
+            for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", text, re.S)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("src")
+    ap.add_argument("-k", "--kernel", default="", help="substring of the kernel symbol")
+    ap.add_argument("flags", nargs="*")
+    a, extra = ap.parse_known_args()
+
+    with tempfile.TemporaryDirectory() as td:
+        asm = os.path.join(td, "k.s")
+        compile_asm(a.src, asm, BASE_FLAGS + a.flags + extra)
+        text = open(asm).read()
+
+    meta = {}
+    for name, lines in kernel_descriptors(text).items():
+        body = "\n".join(lines)
+        g = lambda k: (re.search(r"\.%s (\d+)" % k, body) or [None, "?"])[1]
+        meta[name] = (g("amdhsa_next_free_vgpr"), g("amdhsa_next_free_sgpr"),
+                      g("amdhsa_group_segment_fixed_size"), g("amdhsa_private_segment_fixed_size"))
+
+    for name, lines in split_functions(text).items():
+        if a.kernel not in name or name not in meta:
+            continue
+        ins = [l.strip() for l in lines if l.startswith("\t") and not l.startswith("\t.")]
+        c = dict(valu=0, salu=0, ds=0, glob=0, br=0, wait=0)
+        for i in ins:
+            op = i.split()[0] if i else ""
+            if op.startswith("v_"):
+                c["valu"] += 1
+            elif op.startswith("s_waitcnt"):
+                c["wait"] += 1
+            elif op.startswith("s_cbranch") or op.startswith("s_branch"):
+                c["br"] += 1
+            elif op.startswith("s_"):
+                c["salu"] += 1
+            elif op.startswith("ds_"):
+                c["ds"] += 1
+            elif op.startswith(("global_", "buffer_", "flat_")):
+                c["glob"] += 1
+        v, s, l, p = meta[name]
+        print(f"{name[:90]}\n   vgpr {v} sgpr {s} lds {l} scratch {p} | lines {len(ins)} " +
+              " ".join(f"{k} {n}" for k, n in c.items()))
+
+
+if __name__ == "__main__":
+    main()
