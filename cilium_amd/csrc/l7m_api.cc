@@ -16,6 +16,7 @@
 
 #include "../../include/l7match.h"
 #include "l7m_device.h"
+#include "l7m_dispatch.h"
 #include "l7m_internal.h"
 #include "program.h"
 
@@ -51,6 +52,16 @@ int finish_compile(CompileResult&& cr, uint32_t proto, l7m_ruleset** out, char* 
   rs->info = cr.info;
   rs->names = std::move(cr.names);
   rs->origin = std::move(cr.origin);
+  if (proto == L7M_PROTO_HTTP && rs->program.size() * 4 >= sizeof(HttpHeader)) {
+    // the lean class is a property of the program: decided here, once (L7M_HTTP_GENERIC=1 keeps
+    // every rule set on the generic kernels, for A/B runs and tests)
+    HttpHeader h;
+    std::memcpy(&h, rs->program.data(), sizeof h);
+    const char* e = std::getenv("L7M_HTTP_GENERIC");
+    const bool generic = e && *e && std::strcmp(e, "0") != 0;
+    rs->http_lean = !generic && http_program_lean(h, reinterpret_cast<const DfaDesc*>(rs->program.data() + h.off_dfas),
+                                                  reinterpret_cast<const FieldDesc*>(rs->program.data() + h.off_fields));
+  }
   *out = rs;
   return L7M_OK;
 }
@@ -231,9 +242,12 @@ int launch(const l7m_ruleset* crs, const void* arena, size_t arena_bytes, const 
     std::memcpy(&h, rs->program.data(), sizeof h);
     if (http_stage_bytes(h) == 0) return L7M_ETOOBIG;
     const DfaDesc* dd = reinterpret_cast<const DfaDesc*>(rs->program.data() + h.off_dfas);
+    // the internal launch bits come from the rule set alone, never from the caller's flags
+    flags &= ~kLaunchInternal;
     for (uint32_t k = 0; k < h.n_dfas; ++k)
       if (dd[k].lit_tab != kNone) flags |= kLaunchLiterals;
     if (rs->info.n_dense_dfas) flags |= kLaunchDense;  // (value and forced-capture R automata)
+    if (rs->http_lean) flags |= kLaunchLean;
     e = launch_http(dprog, h, static_cast<const uint8_t*>(arena), arena_bytes, static_cast<const uint64_t*>(offs),
                     n, static_cast<int32_t*>(verdicts), static_cast<unsigned long long*>(hits),
                     stream, cus, flags, done);
@@ -541,6 +555,8 @@ int l7m_ruleset_get_info(const l7m_ruleset* rs, l7m_ruleset_info* out) {
   *out = rs->info;
   return L7M_OK;
 }
+
+int l7m_ruleset_http_lean(const l7m_ruleset* rs) { return rs && rs->proto == L7M_PROTO_HTTP && rs->http_lean ? 1 : 0; }
 
 int l7m_ruleset_program(const l7m_ruleset* rs, void* buf, size_t* len) {
   if (!rs || !len) return L7M_EINVAL;

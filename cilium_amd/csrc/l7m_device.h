@@ -91,6 +91,12 @@ constexpr uint32_t kLaunchLiterals = 1u << 29;  // L7M_FLAG_DIAG_* use bits 30, 
 // ... the program has dense automata (program.h kDfaDense): the instantiation
 // that walks them (l7m_http_impl.h kFeatDense)
 constexpr uint32_t kLaunchDense = 1u << 28;
+// ... the program is of the lean class (l7m_dispatch.h http_program_lean,
+// decided once when the rule set is created): the first pass runs the lean
+// instantiation (l7m_http_impl.h kFeatLean)
+constexpr uint32_t kLaunchLean = 1u << 27;
+// (l7m_api.cc clears these from the flags a caller passes before it sets them)
+constexpr uint32_t kLaunchInternal = kLaunchLiterals | kLaunchDense | kLaunchLean;
 // Completion signal of a first-pass launch (the batcher's latency path):
 // every wave, once its verdicts are visible system-wide, adds one to *ctr
 // (device memory, zero between launches); the last one resets it and stores

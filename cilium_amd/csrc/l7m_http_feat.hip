@@ -21,12 +21,26 @@ namespace {
 
 // First pass of feature set F: hit mode x end-code registers R (4, 8, 0 = LDS
 // columns).  Any other mode counts in global memory, any other R uses columns.
+// lean: the program is of the lean class (l7m_dispatch.h http_program_lean),
+// whose kernels exist for the plain feature set with R = 4 only; any other
+// combination is an error, never another kernel.
 template <int F>
-hipError_t http_main(int mode, int R, dim3 grid, size_t lds, hipStream_t stream, const uint32_t* dprog,
+hipError_t http_main(int mode, int R, bool lean, dim3 grid, size_t lds, hipStream_t stream, const uint32_t* dprog,
                      const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n, int32_t* verdicts,
                      unsigned long long* hits, uint32_t stage, uint32_t* slowq, DoneSignal done) {
   mode = mode == kNoHits || mode == kLdsHits ? mode : kGlobalHits;
   R = R == 4 || R == 8 ? R : 0;
+  if (lean) {
+    if constexpr (F == 0) {
+      if (R != 4) return hipErrorInvalidValue;
+      return dispatch_values<int, kNoHits, kLdsHits, kGlobalHits>(mode, hipErrorInvalidValue, [&](auto M) {
+        return launch_one<decltype(M)::value, 4, 0, kFeatLean>(grid, lds, stream, dprog, arena, arena_bytes, offs, n,
+                                                                verdicts, hits, stage, nullptr, slowq, done);
+      });
+    } else {
+      return hipErrorInvalidValue;
+    }
+  }
   return dispatch_values<int, kNoHits, kLdsHits, kGlobalHits>(mode, hipErrorInvalidValue, [&](auto M) {
     return dispatch_values<int, 4, 8, 0>(R, hipErrorInvalidValue, [&](auto RR) {
       return launch_one<decltype(M)::value, decltype(RR)::value, 0, F>(
@@ -55,13 +69,13 @@ hipError_t http_slow(int R, int tier, const HttpHeader& h, uint32_t blocks, hipS
 
 // The two launch entry points of feature set F.
 #define L7M_FEAT_DEFS(F)                                                                                         \
-  hipError_t L7M_CAT(launch_http_main_f, F)(int mode, int R, dim3 grid, size_t lds, hipStream_t stream,         \
+  hipError_t L7M_CAT(launch_http_main_f, F)(int mode, int R, bool lean, dim3 grid, size_t lds, hipStream_t stream, \
                                             const uint32_t* dprog, const uint8_t* arena, uint64_t arena_bytes,  \
                                             const uint64_t* offs, uint64_t n, int32_t* verdicts,                \
                                             unsigned long long* hits, uint32_t stage, uint32_t* slowq,          \
                                             DoneSignal done) {                                                   \
-    return http_main<F>(mode, R, grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, stage,  \
-                        slowq, done);                                                                            \
+    return http_main<F>(mode, R, lean, grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits,    \
+                        stage, slowq, done);                                                                     \
   }                                                                                                              \
   hipError_t L7M_CAT(launch_http_slow_f, F)(int R, int tier, const HttpHeader& h, uint32_t blocks,              \
                                             hipStream_t stream, const uint32_t* dprog, const uint8_t* arena,    \

@@ -14,6 +14,8 @@
 #include "program.h"
 #include "regex_vm.h"
 
+#include <type_traits>
+
 namespace l7m {
 namespace {
 
@@ -343,6 +345,17 @@ struct LdsChain {
       L7M_OSTEP(b, "BYTE_0", pw, "BYTE_3", true)
       pw = b << 24;
     }
+  }
+  // The end code of a table whose entries carry it (lds_es == kLdsEsInEntry),
+  // from the table's latch list and start latch: all the lean kernel needs.
+  __device__ __forceinline__ uint32_t code_in_entry(const uint32_t* __restrict__ img, uint32_t lds_latch,
+                                                    uint32_t start_latch) const {
+    if (dead_now() || (e >> (kLdsRowShift + 2)) == t0) return 0;
+    const uint32_t es = (e >> 8) & 0xffu;
+    if (es != kEs8Latched) return es;
+    const uint32_t last = slast == kNone ? kNone : ((slast & 0xffffffu) >> 2) - t0;
+    const uint16_t* I16 = reinterpret_cast<const uint16_t*>(img);
+    return kLatchedBit | (last == kNone ? start_latch : I16[lds_latch + last]);
   }
   __device__ __forceinline__ uint32_t code(const uint32_t* __restrict__ img, const uint32_t* __restrict__ prog,
                                            const DfaDesc& dd) const {
@@ -807,8 +820,8 @@ __device__ __forceinline__ uint32_t walk_dfa(const Ctx& c, uint32_t d, const Src
 // the LDS header-name table (program.h): the name's words are read aligned
 // and hashed word-wise, one slot probe, one word-wise compare.  kNone if no
 // rule references the name.
-template <class Src>
-__device__ __forceinline__ uint32_t name_field_of(const Ctx& c, const HttpHeader& h, const Src& src, uint32_t pos,
+template <class H, class Src>
+__device__ __forceinline__ uint32_t name_field_of(const Ctx& c, const H& h, const Src& src, uint32_t pos,
                                                   uint32_t len) {
   constexpr uint32_t kW = kNameHashMinWords;
   const uint32_t sh = pos & 3u, w0 = pos >> 2;
@@ -938,6 +951,54 @@ constexpr int32_t kNeedVerify = INT32_MIN;
 // Programs without them run the plain instantiation, whose code and register
 // allocation no feature touches.
 constexpr int kFeatLit = 1, kFeatDcap = 2, kFeatDense = 4;
+// kFeatLean (first pass only, alone, with four end-code registers): the
+// program is of the lean class (l7m_dispatch.h http_program_lean).  The
+// clauses of that predicate are compile-time constants of the instantiation,
+// and what it still needs of the program header is read once per wave before
+// the tile loop (LeanHeader): the generic kernels are out of scalar registers and re-read those words in
+// every tile, each read followed by a wait that also drains the LDS reads in
+// flight.
+constexpr int kFeatLean = 8;
+
+// A value the compiler can neither re-load nor recompute inside the tile loop
+// (a scalar load is rematerialisable; this is not): it stays in a scalar
+// register or a lane of a spill register.
+__device__ __forceinline__ uint32_t keep_scalar(uint32_t v) {
+  v = __builtin_amdgcn_readfirstlane(v);
+  asm volatile("" : "+s"(v));
+  return v;
+}
+
+// The lean kernel's stand-in for HttpHeader in eval_walk / eval_verify: the
+// members they read carry HttpHeader's names, so either type fits.
+struct LeanHeader {
+  static constexpr uint32_t n_dfas = 4;  // an upper bound (the end codes' register file)
+  static constexpr uint32_t cand_dfas_hi = 0;
+  static constexpr uint32_t lds_dcap = kNone;
+  uint32_t name_len_lo, name_len_hi, lds_name_tab, name_tab_mask;
+  uint32_t cand_dfas_lo, pres_fields_lo, pres_fields_hi, always_rule;
+  Span zero_list;
+};
+__device__ __forceinline__ LeanHeader make_lean_header(const HttpHeader& h) {
+  LeanHeader l;
+  l.name_len_lo = keep_scalar(h.name_len_lo);
+  l.name_len_hi = keep_scalar(h.name_len_hi);
+  l.lds_name_tab = keep_scalar(h.lds_name_tab);
+  l.name_tab_mask = keep_scalar(h.name_tab_mask);
+  l.cand_dfas_lo = keep_scalar(h.cand_dfas_lo);
+  l.pres_fields_lo = keep_scalar(h.pres_fields_lo);
+  l.pres_fields_hi = keep_scalar(h.pres_fields_hi);
+  l.always_rule = keep_scalar(h.always_rule);
+  l.zero_list.off = keep_scalar(h.zero_list.off);
+  l.zero_list.len = keep_scalar(h.zero_list.len);
+  return l;
+}
+// The header the tile loop reads: the program's, or the lean kernel's copy.
+template <bool kLean>
+__device__ __forceinline__ decltype(auto) tile_header(const HttpHeader& h) {
+  if constexpr (kLean) return make_lean_header(h);
+  else return (h);
+}
 // First pass: the request's smallest candidate may be a slow-path rule
 // (kCrSlow): it is queued for http_slow_kernel, which decides it exactly.
 constexpr int32_t kDeferred = INT32_MIN + 1;
@@ -985,11 +1046,15 @@ __device__ bool field_at(const Ctx& c, const HttpHeader& h, const Src& src, uint
 // when it is decided without rules, else kNeedVerify with `o` filled in.
 // kAblate (diagnostic builds selected by L7M_FLAG_DIAG_*; verdicts invalid):
 // 1 = stop after the DFA walks, 2 = stop after record validation.
-template <int kReg, int kAblate, int kFeat, class Src>
-__device__ __forceinline__ int32_t eval_walk(const Ctx& c, const HttpHeader& h, const Src& src, uint64_t limit,
+// H: HttpHeader, or LeanHeader in the lean kernel (kFeatLean).
+template <int kReg, int kAblate, int kFeat, class H, class Src>
+__device__ __forceinline__ int32_t eval_walk(const Ctx& c, const H& h, const Src& src, uint64_t limit,
                                              WalkOut<kReg>& o, uint64_t (&prof)[8]) {
   if constexpr (kProf && Src::kLds) prof[0] = __builtin_amdgcn_s_memtime();
   constexpr bool kLit = (kFeat & kFeatLit) != 0, kDcap = (kFeat & kFeatDcap) != 0, kDense = (kFeat & kFeatDense) != 0;
+  constexpr bool kLean = (kFeat & kFeatLean) != 0;
+  static_assert(kLean == std::is_same<H, LeanHeader>::value, "the lean kernel reads its own header copy");
+  static_assert(!kLean || (kReg == 4 && kAblate == 0 && kFeat == kFeatLean), "lean: four code registers, no feature");
   Codes<kReg>& codes = o.codes;
   if (limit < L7M_HTTP_REC_FIXED) return L7M_VERDICT_PARSE_ERROR;
   const uint32_t w0 = src.word(0), w1 = src.word(1), w2 = src.word(2), w3 = src.word(3), w4 = src.word(4);
@@ -1015,7 +1080,9 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const HttpHeader& h, 
   bool h0 = true;
   {
     const uint32_t pol = w4 >> 16;
-    if (h.single_entry) {
+    if constexpr (kLean) {  // single entry, with L7 rules
+      if (pol != 0) return L7M_VERDICT_DENY;
+    } else if (h.single_entry) {
       if (pol != 0) return L7M_VERDICT_DENY;  // unknown endpoint policy (h:231-235)
       if (h.allow_no_l7) return L7M_VERDICT_ALLOW_NO_L7;
     } else {
@@ -1071,7 +1138,8 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const HttpHeader& h, 
       if (flags & (job == 0 ? L7M_HTTP_F_METHOD : job == 1 ? L7M_HTTP_F_PATH : L7M_HTTP_F_AUTHORITY)) f = job;
       pos += len;
     } else {
-      if (!h.has_name_dfa) break;
+      if constexpr (!kLean)  // (lean: without a name table the masks are empty, http_program_lean)
+        if (!h.has_name_dfa) break;
       uint32_t e = 0;
       for (; hj < nhdr; ++hj) {
         e = src.word(5 + hj);
@@ -1082,7 +1150,7 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const HttpHeader& h, 
       if (!__any(hj < nhdr)) break;
       if (hj < nhdr) {
         const uint32_t nl = e & 0xffffu, vl = e >> 16;
-        if (h.lds_name_tab != kNone) {
+        if (kLean || h.lds_name_tab != kNone) {
           f = name_field_of(c, h, src, hp, nl);
         } else {
           const uint32_t code = walk_dfa<false, false, false>(c, h.n_dfas, src, hp, nl);
@@ -1097,7 +1165,25 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const HttpHeader& h, 
       }
     }
     HPROF(2);  // job selection, header-name lookup
-    if (f != kNone) {
+    if constexpr (kLean) {
+      // every automaton is walked from LDS and its entries carry the end code
+      if (f != kNone) {
+        present |= 1ull << f;
+        const FieldDesc& fd = c.fields[f];  // (descriptors per lane, as the generic kernel reads them)
+        for (uint32_t k = 0; k < fd.ndfa; ++k) {
+          const uint32_t d = fd.dfa_first + k;
+          const DfaDesc& dd = c.dds[d];
+          LdsChain ch;
+          ch.init(dd);
+          if (!dd.start_base) ch.e = 0;  // dead from the start: the dead row (walk_lds skips the walk: the same code, 0)
+          ch.run(src, p, len, 0);
+          const uint32_t code = ch.code_in_entry(c.img, dd.lds_latch, dd.start_latch);
+          HPROF(3);
+          codes.set(d, code);
+          touch(d, code);
+        }
+      }
+    } else if (f != kNone) {
       present |= 1ull << f;
       const FieldDesc& fd = c.fields[f];
       uint32_t kend = fd.ndfa;
@@ -1182,9 +1268,10 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const HttpHeader& h, 
 // decided by the executor of regex_vm.h on the record's field values (src,
 // vm: this lane's scratch); in the first pass such a rule whose automaton
 // checks pass only marks the request for deferral.
-template <int kReg, int kSlowPass = 0, bool kDcap = false, class Src = GlbSrc>
-__device__ __forceinline__ int32_t eval_verify(const Ctx& c, const HttpHeader& h, const WalkOut<kReg>& o,
+template <int kReg, int kSlowPass = 0, bool kDcap = false, class Src = GlbSrc, class H = HttpHeader>
+__device__ __forceinline__ int32_t eval_verify(const Ctx& c, const H& h, const WalkOut<kReg>& o,
                                                const Src* src = nullptr, uint32_t* vm = nullptr) {
+  constexpr bool kLean = std::is_same<H, LeanHeader>::value;  // (no slow-path rules)
   const Codes<kReg>& codes = o.codes;
   const uint64_t present = o.present;
   asm volatile("" ::"v"(o.pf_t));  // the touch completes here, not at its first use
@@ -1213,7 +1300,7 @@ __device__ __forceinline__ int32_t eval_verify(const Ctx& c, const HttpHeader& h
   // A candidate whose checks passed: rules with slow-path matchers are
   // deferred (first pass) or run through the executor (slow pass).
   auto take = [&](uint32_t rid, uint32_t hd) -> bool {
-    if (!(hd & kCrSlow)) {
+    if (kLean || !(hd & kCrSlow)) {
       best = rid;
       return true;
     }
@@ -1430,6 +1517,7 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
                                                uint32_t nparts, uint32_t wave_index, uint32_t wave_count,
                                                DoneSignal done = DoneSignal{nullptr, nullptr, 0}) {
   extern __shared__ __align__(16) uint32_t smem[];
+  constexpr bool kLean = (kFeat & kFeatLean) != 0;
   const HttpHeader& h = *reinterpret_cast<const HttpHeader*>(prog);
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
   uint32_t* img = smem;
@@ -1487,6 +1575,7 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
   __syncthreads();
 
   const Ctx c = make_ctx(prog, img, h);
+  const auto& th = tile_header<kLean>(h);  // what the tile loop reads of the header
   uint32_t* mycol = col + tid;
   // diagnostic wave timeline per tile (kProf, s_memtime): [0] top wait,
   // [1] walks, [2] entry wait, [3] issue, [4] verify + store, [5] counters;
@@ -1594,14 +1683,14 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
         const LdsSrc s{reinterpret_cast<const uint32_t*>(stg + (o - base))};
         const uint32_t w0 = s.word(0);
         if (((static_cast<uint64_t>(w0) + 3) & ~3ull) <= onext - o) {
-          v = eval_walk<kReg, kAblate, kFeat>(c, h, s, onext - o, wo, prof);
+          v = eval_walk<kReg, kAblate, kFeat>(c, th, s, onext - o, wo, prof);
           done = true;
         }
       }
       if (!done) {  // outside the staged window: read HBM directly
         const bool inb = (o & 3) == 0 && o + L7M_HTTP_REC_FIXED <= arena_bytes;
         const GlbSrc s{reinterpret_cast<const uint32_t*>(arena + (inb ? o : 0))};
-        v = inb ? eval_walk<kReg, kAblate, kFeat>(c, h, s, arena_bytes - o, wo, prof) : L7M_VERDICT_PARSE_ERROR;
+        v = inb ? eval_walk<kReg, kAblate, kFeat>(c, th, s, arena_bytes - o, wo, prof) : L7M_VERDICT_PARSE_ERROR;
       }
     }
     qtn(1);
@@ -1614,7 +1703,7 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
     load_offs(t2.cur + t2.take, &o2, &n2);
     qtn(3);
     if (lane < take) {
-      if (v == kNeedVerify) v = eval_verify<kReg, 0, (kFeat & kFeatDcap) != 0>(c, h, wo);
+      if (v == kNeedVerify) v = eval_verify<kReg, 0, (kFeat & kFeatDcap) != 0>(c, th, wo);
       verdicts[t.cur + lane] = v;
       if (v == kDeferred) {  // decided by http_slow_kernel (rules with slow-path matchers)
         const uint32_t at = atomicAdd(slowq, 1u);

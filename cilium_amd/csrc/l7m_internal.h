@@ -88,6 +88,7 @@ struct l7m_ruleset {
   l7m_ruleset_info info{};
   std::vector<std::string> names;       // HTTP endpoint policy names
   std::vector<l7m_rule_origin> origin;  // HTTP verdict index -> NPDS position
+  bool http_lean = false;               // HTTP: launched with kLaunchLean (l7m_dispatch.h http_program_lean)
   std::mutex mu;
   void* dprog[64] = {nullptr};  // per HIP device
 };

@@ -29,7 +29,8 @@ namespace l7m {
 // First-pass / slow-pass launches of the ECMAScript instantiations of one
 // feature set (l7m_http_feat.hip, compiled once per kFeat)
 #define L7M_FEAT_DECL(F)                                                                                            \
-  hipError_t launch_http_main_f##F(int mode, int R, dim3 grid, size_t lds, hipStream_t stream, const uint32_t* dprog,  \
+  hipError_t launch_http_main_f##F(int mode, int R, bool lean, dim3 grid, size_t lds, hipStream_t stream,              \
+                                   const uint32_t* dprog,                                                              \
                                    const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n,        \
                                    int32_t* verdicts, unsigned long long* hits, uint32_t stage, uint32_t* slowq,       \
                                    DoneSignal done);                                                                   \
@@ -155,8 +156,9 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
                                                            launch_http_slow_f6, launch_http_slow_f7};
   // the completion signal only where this launch decides every request
   const DoneSignal sig = done && !h.n_slow ? *done : DoneSignal{nullptr, nullptr, 0};
-  hipError_t e = mains[feat](mode, R, grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, stage,
-                             slowq, sig);
+  // (kLaunchLean: the lean kernels of the plain feature set; an error for any other)
+  hipError_t e = mains[feat](mode, R, (flags & kLaunchLean) != 0, grid, lds, stream, dprog, arena, arena_bytes, offs, n,
+                             verdicts, hits, stage, slowq, sig);
   if (h.n_slow) {
     for (int tier = 1; tier <= 2 && e == hipSuccess; ++tier)
       e = slows[feat](R, tier, h, tier == 1 ? blocks1 : blocks2, stream, dprog, arena, arena_bytes, offs, n, verdicts,

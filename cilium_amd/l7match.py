@@ -74,7 +74,7 @@ EXPORTED_SYMBOLS = (
     "l7m_multi_create", "l7m_multi_destroy", "l7m_multi_uses_rccl", "l7m_shard_bounds", "l7m_multi_eval",
     "l7m_multi_eval_device",
     "l7m_http_wire_arena_bound", "l7m_http_wire_decode", "l7m_http_wire_decode_device", "l7m_http_wire_encode",
-    "l7m_batcher_eval_http_wire",
+    "l7m_batcher_eval_http_wire", "l7m_ruleset_http_lean",
 )
 
 
@@ -271,6 +271,7 @@ def _load() -> ctypes.CDLL:
     lib.l7m_retain.argtypes = [P]
     lib.l7m_retain.restype = None
     lib.l7m_ruleset_get_info.argtypes = [P, ctypes.POINTER(_Info)]
+    lib.l7m_ruleset_http_lean.argtypes = [P]
     lib.l7m_ruleset_program.argtypes = [P, P, ctypes.POINTER(sz)]
     lib.l7m_http_translate.argtypes = [ctypes.POINTER(_HttpRule), ctypes.POINTER(_Matcher), sz,
                                        ctypes.c_char_p, sz]
@@ -625,6 +626,12 @@ class RuleSet:
     @property
     def n_counters(self) -> int:
         return int(self.info.n_counters)
+
+    @property
+    def http_lean(self) -> bool:
+        """Whether the first pass of this HTTP rule set runs the lean kernel
+        (l7m_ruleset_http_lean; L7M_HTTP_GENERIC=1 at compile time forces the generic one)."""
+        return bool(_lib.l7m_ruleset_http_lean(self._h))
 
     def program(self) -> np.ndarray:
         n = ctypes.c_size_t(0)

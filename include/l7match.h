@@ -265,6 +265,12 @@ int l7m_ruleset_rule_origin(const l7m_ruleset* rs, uint32_t rule, l7m_rule_origi
 void l7m_retain(l7m_ruleset* rs);
 void l7m_release(l7m_ruleset* rs);
 int l7m_ruleset_get_info(const l7m_ruleset* rs, l7m_ruleset_info* out);
+/* 1 if the HTTP rule set's first pass runs the lean kernel (a single-entry
+ * program without slow-path rules, forced captures, literal tables or dense
+ * automata whose <= 4 value automata are walked from LDS), else 0.  Decided
+ * when the rule set is compiled; L7M_HTTP_GENERIC=1 in the environment at
+ * that time keeps every rule set on the generic kernels. */
+int l7m_ruleset_http_lean(const l7m_ruleset* rs);
 /* Copy of the packed device program (for inspection / tests).  *len receives
  * the size; when buf is NULL only the size is returned. */
 int l7m_ruleset_program(const l7m_ruleset* rs, void* buf, size_t* len);

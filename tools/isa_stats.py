@@ -5,7 +5,10 @@ on code generation without a GPU:
     tools/isa_stats.py cilium_amd/csrc/l7m_kafka.hip [-DFLAG ...] [-k substr]
 
 Prints per kernel: VGPR / SGPR / LDS / scratch from the code object metadata
-and instruction counts by class (VALU, SALU, DS, global, branches, waitcnt).
+and instruction counts by class (VALU, SALU, DS, global, branches, waitcnt),
+the code bytes, the scalar loads (all, and those in basic blocks the compiler
+marks as part of a loop), and the SGPR spill traffic to VGPR lanes
+(v_writelane / v_readlane).
 The compile and the assembly parsing are shared with tools/isa_diff.py.
 """
 import argparse
@@ -45,18 +48,51 @@ def kernel_descriptors(text):
             for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", text, re.S)}
 
 
+def code_bytes(text):
+    """{symbol: codeLenInByte of the compiler's per-function summary}."""
+    return {m.group(1): int(m.group(2))
+            for m in re.finditer(r"^\t\.size\t(\S+), \.Lfunc_end\d+-\S+\n(?:.*\n)*?; codeLenInByte = (\d+)", text, re.M)}
+
+
+def loop_counts(lines):
+    """(scalar loads, scalar loads in loop blocks, v_writelane, v_readlane) of one function."""
+    in_loop, at_label, n = False, False, dict(sload=0, sload_loop=0, wlane=0, rlane=0)
+    for l in lines:
+        if re.match(r"^\.LBB\d+_\d+:", l):
+            in_loop, at_label = "in Loop" in l or "Loop Header" in l, True
+            continue
+        if at_label and l.lstrip().startswith(";"):  # a named block carries the loop note on the comment lines below its label
+            in_loop |= "in Loop" in l or "Loop Header" in l
+            continue
+        at_label = False
+        op = l.split()[0] if l.startswith("\t") and l.split() else ""
+        if op.startswith("s_load_") or op.startswith("s_buffer_load_"):
+            n["sload"] += 1
+            n["sload_loop"] += in_loop
+        elif op.startswith("v_writelane"):
+            n["wlane"] += 1
+        elif op.startswith("v_readlane"):
+            n["rlane"] += 1
+    return n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("src")
     ap.add_argument("-k", "--kernel", default="", help="substring of the kernel symbol")
+    ap.add_argument("--asm", action="store_true", help="src is assembly already compiled (compile_asm's output)")
     ap.add_argument("flags", nargs="*")
     a, extra = ap.parse_known_args()
 
-    with tempfile.TemporaryDirectory() as td:
-        asm = os.path.join(td, "k.s")
-        compile_asm(a.src, asm, BASE_FLAGS + a.flags + extra)
-        text = open(asm).read()
+    if a.asm:
+        text = open(a.src).read()
+    else:
+        with tempfile.TemporaryDirectory() as td:
+            asm = os.path.join(td, "k.s")
+            compile_asm(a.src, asm, BASE_FLAGS + a.flags + extra)
+            text = open(asm).read()
 
+    size = code_bytes(text)
     meta = {}
     for name, lines in kernel_descriptors(text).items():
         body = "\n".join(lines)
@@ -84,7 +120,8 @@ def main():
             elif op.startswith(("global_", "buffer_", "flat_")):
                 c["glob"] += 1
         v, s, l, p = meta[name]
-        print(f"{name[:90]}\n   vgpr {v} sgpr {s} lds {l} scratch {p} | lines {len(ins)} " +
+        c.update(loop_counts(lines))
+        print(f"{name[:90]}\n   vgpr {v} sgpr {s} lds {l} scratch {p} code_bytes {size.get(name, '?')} | lines {len(ins)} " +
               " ".join(f"{k} {n}" for k, n in c.items()))
 
 
