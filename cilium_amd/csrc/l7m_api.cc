@@ -17,6 +17,7 @@
 #include "../../include/l7match.h"
 #include "l7m_device.h"
 #include "l7m_dispatch.h"
+#include "l7m_http_log.h"
 #include "l7m_internal.h"
 #include "program.h"
 
@@ -667,6 +668,57 @@ int l7m_http_wire_decode_device(const void* d_wire, size_t wire_bytes, const voi
       static_cast<uint64_t*>(d_rec_offsets), static_cast<int32_t*>(d_status), static_cast<uint64_t*>(d_arena_bytes),
       static_cast<hipStream_t>(hip_stream));
   return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+}
+
+int l7m_http_access_log_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
+                               const void* d_verdicts, const l7m_access_log_opts* opts, uint32_t select, void* d_out,
+                               size_t cap, void* d_entry_offs, void* d_total, void* hip_stream) {
+  if (!d_total || (n && (!d_arena || !d_rec_offsets || !d_verdicts || !d_entry_offs)) || (cap && !d_out) ||
+      (select & ~(L7M_LOG_FORWARDED | L7M_LOG_DENIED)))
+    return L7M_EINVAL;
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return L7M_EINVAL;
+  const l7m_access_log_opts o = log_norm_opts(opts);
+  for (const char* s : {o.policy_name, o.source_address, o.destination_address})
+    if (s && std::strlen(s) > kLogStringMax) return L7M_EINVAL;
+  std::string head, policy, addrs;
+  log_const_fields(o, &head, &policy, &addrs);
+  LogConstsFixed c;
+  std::memset(&c, 0, sizeof c);
+  if (head.size() > sizeof c.head || policy.size() > sizeof c.policy || addrs.size() > sizeof c.addrs)
+    return L7M_EINVAL;
+  std::memcpy(c.head, head.data(), head.size());
+  std::memcpy(c.policy, policy.data(), policy.size());
+  std::memcpy(c.addrs, addrs.data(), addrs.size());
+  c.head_len = static_cast<uint32_t>(head.size());
+  c.policy_len = static_cast<uint32_t>(policy.size());
+  c.addrs_len = static_cast<uint32_t>(addrs.size());
+  c.local_identity = o.local_identity;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
+  const hipError_t e = launch_http_log(
+      static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets), n,
+      static_cast<const int32_t*>(d_verdicts), c, select ? select : (L7M_LOG_FORWARDED | L7M_LOG_DENIED),
+      static_cast<uint8_t*>(d_out), cap, static_cast<uint64_t*>(d_entry_offs), static_cast<uint64_t*>(d_total),
+      static_cast<hipStream_t>(hip_stream));
+  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+}
+
+int l7m_proxy_stats_update_device(l7m_proxy_stats_table* t, uint32_t proto, const void* d_arena, size_t arena_bytes,
+                                  const void* d_rec_offsets, const void* d_verdicts, size_t n, uint16_t port,
+                                  int ingress, void* hip_stream) {
+  // Kafka: keyed by the caller's own (port, ingress); see include/l7match.h
+  if (!t || proto != L7M_PROTO_HTTP || (n && (!d_arena || !d_rec_offsets || !d_verdicts))) return L7M_EINVAL;
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return L7M_EINVAL;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
+  std::vector<uint64_t> counters(kStatsCounters);
+  const hipError_t e = launch_http_stats(
+      static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets),
+      static_cast<const int32_t*>(d_verdicts), n, (ingress ? 65536u : 0u) | port, counters.data(),
+      static_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+  proxy_stats_merge_http(t, counters.data());
+  return L7M_OK;
 }
 
 int l7m_eval_device(const l7m_ruleset* rs, const void* d_arena, size_t arena_bytes,

@@ -121,6 +121,21 @@ hipError_t launch_http_wire(const uint8_t* wire, uint64_t wire_bytes, const uint
                             const l7m_http_wire_meta* meta, uint8_t* arena, uint64_t cap, uint64_t* rec_offsets,
                             int32_t* status, uint64_t* total, hipStream_t stream);
 
+// HttpLogEntry messages of a decided batch (l7m_http_log.hip): measure pass,
+// scan and emit pass enqueued on `stream`.  entry_offs (u64[n + 1]) and *total
+// are always written; nothing of `out` is when the total exceeds cap.
+struct LogConstsFixed;
+hipError_t launch_http_log(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n,
+                           const int32_t* verdicts, const LogConstsFixed& c, uint32_t select, uint8_t* out,
+                           uint64_t cap, uint64_t* entry_offs, uint64_t* total, hipStream_t stream);
+// Request counters of a decided HTTP batch per (direction, port, verdict
+// class) into host_counters (l7m_http_log.h kStatsCounters words; caller_row =
+// ingress * 65536 + port for records that do not validate).  Synchronises
+// `stream`.
+hipError_t launch_http_stats(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs,
+                             const int32_t* verdicts, uint64_t n, uint32_t caller_row, uint64_t* host_counters,
+                             hipStream_t stream);
+
 // Mailbox of a resident evaluator (l7m_kafka.hip kafka_resident_kernel),
 // in pinned, device-mapped host memory.  The host fills slot seq %
 // kResidentSlots, then raises post_seq to seq (release); the workgroup

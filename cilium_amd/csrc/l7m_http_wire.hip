@@ -20,13 +20,13 @@
 
 #include "l7m_device.h"
 #include "l7m_http_wire.h"
+#include "l7m_tile_scan.h"
 
 namespace l7m {
 namespace {
 
-constexpr uint32_t kWireTile = 256;            // heads per workgroup = threads per workgroup
+constexpr uint32_t kWireTile = kTileThreads;   // heads per workgroup = threads per workgroup (l7m_tile_scan.h)
 constexpr uint32_t kWireStage = 64u * 1024u;   // staged wire bytes per chunk (256 per head)
-constexpr uint32_t kScanThreads = 1024;
 
 // A staged head, read a byte at a time.  (Keeping an aligned 8-byte window of
 // the stage in registers, one ds_read_b64 per eight bytes, measured slower:
@@ -129,19 +129,6 @@ __device__ __forceinline__ void for_each_head(uint8_t* lds, const uint8_t* wire,
   }
 }
 
-// Inclusive sum over the workgroup (kWireTile threads) in LDS.
-__device__ __forceinline__ uint64_t block_inclusive(uint64_t v, uint64_t* tmp /* LDS, kWireTile */) {
-  tmp[threadIdx.x] = v;
-  __syncthreads();
-  for (uint32_t d = 1; d < kWireTile; d <<= 1) {
-    const uint64_t add = threadIdx.x >= d ? tmp[threadIdx.x - d] : 0;
-    __syncthreads();
-    tmp[threadIdx.x] += add;
-    __syncthreads();
-  }
-  return tmp[threadIdx.x];
-}
-
 __global__ __launch_bounds__(kWireTile) void http_wire_measure(const uint8_t* wire, uint64_t wire_bytes,
                                                                const uint64_t* head_offs, uint64_t n,
                                                                uint64_t* sizes /* = rec_offsets */, int32_t* status,
@@ -164,33 +151,6 @@ __global__ __launch_bounds__(kWireTile) void http_wire_measure(const uint8_t* wi
   });
   const uint64_t incl = block_inclusive(size, tile_lo);
   if (threadIdx.x == kWireTile - 1) tile_sums[blockIdx.x] = incl;
-}
-
-// tile_sums[0, tiles) -> exclusive sums in place, *total.  One workgroup: each
-// thread sums a contiguous share, the shares are scanned in LDS.
-__global__ __launch_bounds__(kScanThreads) void http_wire_scan_tiles(uint64_t* tile_sums, uint64_t tiles,
-                                                                     uint64_t* total) {
-  __shared__ uint64_t part[kScanThreads];
-  const uint64_t per = (tiles + kScanThreads - 1) / kScanThreads;
-  const uint64_t lo = per * threadIdx.x < tiles ? per * threadIdx.x : tiles;
-  const uint64_t hi = lo + per < tiles ? lo + per : tiles;
-  uint64_t s = 0;
-  for (uint64_t t = lo; t < hi; ++t) s += tile_sums[t];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (uint32_t d = 1; d < kScanThreads; d <<= 1) {
-    const uint64_t add = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-    __syncthreads();
-    part[threadIdx.x] += add;
-    __syncthreads();
-  }
-  uint64_t run = part[threadIdx.x] - s;
-  for (uint64_t t = lo; t < hi; ++t) {
-    const uint64_t v = tile_sums[t];
-    tile_sums[t] = run;
-    run += v;
-  }
-  if (threadIdx.x == kScanThreads - 1) *total = part[threadIdx.x];
 }
 
 __global__ __launch_bounds__(kWireTile) void http_wire_emit(const uint8_t* wire, uint64_t wire_bytes,

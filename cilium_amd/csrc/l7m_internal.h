@@ -71,6 +71,18 @@ CompileResult compile_kafka(const l7m_kafka_rule* rules, size_t n, const l7m_opt
 CompileResult compile_kafka_map(const l7m_kafka_selector_rules* map, size_t n_entries,
                                 const l7m_identity_selectors* ids, size_t n_ids, const l7m_opts& opts);
 
+
+// Side effects (l7m_side.cc), for the device entry points of l7m_api.cc.
+// The caller's access-log options with the struct_size rule and the defaults
+// of l7m_http_access_log applied ...
+l7m_access_log_opts log_norm_opts(const l7m_access_log_opts* opts);
+// ... and the parts of an HttpLogEntry they fix for a whole call, serialised:
+// fields 1-2, field 4, fields 7-8 (l7m_http_log.h Consts).
+void log_const_fields(const l7m_access_log_opts& o, std::string* head, std::string* policy, std::string* addrs);
+// Adds the HTTP request counters a device pass collected to the table:
+// counters[(ingress * 65536 + port) * 3 + FlowVerdict] (l7m_http_log.h kStats*).
+void proxy_stats_merge_http(l7m_proxy_stats_table* t, const uint64_t* counters);
+
 }  // namespace l7m
 
 // The opaque handle.  Immutable after compile except for the per-device

@@ -26,6 +26,8 @@
 #include <vector>
 
 #include "../../include/l7match.h"
+#include "l7m_http_log.h"
+#include "l7m_internal.h"
 #include "program.h"
 
 namespace {
@@ -272,47 +274,58 @@ bool kafka_rec(const uint8_t* arena, size_t arena_bytes, uint64_t o, size_t* len
   return true;
 }
 
-// HTTP record fields (include/l7match.h record layout); false if malformed.
-struct HttpView {
-  uint32_t remote_id = 0, dport = 0, flags = 0, nhdr = 0;
-  const uint8_t *method = nullptr, *path = nullptr, *authority = nullptr;
-  uint32_t mlen = 0, plen = 0, alen = 0;
-  const uint8_t* dir = nullptr;   // n_hdr x {u16 name_len, u16 value_len}
-  const uint8_t* names = nullptr; // first header name
-};
-bool http_rec(const uint8_t* arena, size_t arena_bytes, uint64_t o, HttpView* v) {
-  if ((o & 3) || o > arena_bytes || arena_bytes - o < L7M_HTTP_REC_FIXED) return false;
-  const uint8_t* r = arena + o;
-  uint32_t w[5];
-  std::memcpy(w, r, sizeof w);
-  if (w[0] > arena_bytes - o) return false;
-  v->remote_id = w[1];
-  v->dport = w[2] & 0xffffu;
-  v->flags = (w[2] >> 16) & 0xffu;
-  v->nhdr = w[2] >> 24;
-  v->mlen = w[3] & 0xffffu;
-  v->plen = w[3] >> 16;
-  v->alen = w[4] & 0xffffu;
-  uint64_t need = L7M_HTTP_REC_FIXED + 4ull * v->nhdr + v->mlen + v->plen + v->alen;
-  if (need > w[0]) return false;
-  v->dir = r + L7M_HTTP_REC_FIXED;
-  for (uint32_t j = 0; j < v->nhdr; ++j) {
-    uint32_t e;
-    std::memcpy(&e, v->dir + 4 * j, 4);
-    need += (e & 0xffffu) + (e >> 16);
+// The host's instantiation of l7m_http_log.h: the arena in host memory, an
+// entry written where the caller's buffer has room for it.
+struct HostSrc {
+  const uint8_t* p;
+  uint8_t at(uint64_t i) const { return p[i]; }
+  uint32_t word(uint64_t i) const {
+    uint32_t w;
+    std::memcpy(&w, p + i, 4);
+    return w;
   }
-  if (need != w[0]) return false;
-  v->method = v->dir + 4u * v->nhdr;
-  v->path = v->method + v->mlen;
-  v->authority = v->path + v->plen;
-  v->names = v->authority + v->alen;
-  return true;
-}
+};
+struct HostSink {
+  uint8_t* p;
+  void put(uint8_t b) { *p++ = b; }
+};
+struct HostConsts {  // fields 1-2, 4, 7-8 of every entry of a call
+  std::string head, policy, addrs;
+  size_t head_len = 0, policy_len = 0, addrs_len = 0;
+  uint32_t local_identity = 0;
+};
 
-// FlowVerdict of a decided request: 0 Forwarded, 1 Denied, 2 Error.
-uint32_t flow_verdict(int32_t v) { return v >= 0 ? 0u : v == L7M_VERDICT_DENY ? 1u : 2u; }
+using l7m::flow_verdict;
 
 }  // namespace
+
+namespace l7m {
+
+l7m_access_log_opts log_norm_opts(const l7m_access_log_opts* opts) {
+  l7m_access_log_opts o{};
+  o.http_protocol = 1;  // HTTP11: Envoy's default branch (accesslog.cc:68-79)
+  if (opts) {
+    const size_t k = opts->struct_size == 0 || opts->struct_size > sizeof o ? sizeof o : opts->struct_size;
+    std::memcpy(&o, opts, k);
+  }
+  return o;
+}
+
+void log_const_fields(const l7m_access_log_opts& o, std::string* head, std::string* policy, std::string* addrs) {
+  Pb pb;
+  pb.u64(1, o.timestamp_ns);
+  pb.u64(2, o.http_protocol);
+  *head = pb.b;
+  pb.b.clear();
+  pb.bytes(4, o.policy_name, o.policy_name ? std::strlen(o.policy_name) : 0);
+  *policy = pb.b;
+  pb.b.clear();
+  pb.bytes(7, o.source_address, o.source_address ? std::strlen(o.source_address) : 0);
+  pb.bytes(8, o.destination_address, o.destination_address ? std::strlen(o.destination_address) : 0);
+  *addrs = pb.b;
+}
+
+}  // namespace l7m
 
 extern "C" {
 
@@ -464,67 +477,28 @@ int64_t l7m_http_access_log(const uint8_t* arena, size_t arena_bytes, const uint
                             const int32_t* verdicts, const l7m_access_log_opts* opts, uint8_t* out, size_t cap,
                             uint64_t* entry_offs) {
   if (n && (!arena || !offs || !verdicts || !entry_offs)) return L7M_EINVAL;
-  l7m_access_log_opts o{};
-  o.http_protocol = 1;  // HTTP11: Envoy's default branch (accesslog.cc:68-79)
-  if (opts) {
-    const size_t k = opts->struct_size == 0 || opts->struct_size > sizeof o ? sizeof o : opts->struct_size;
-    std::memcpy(&o, opts, k);
-  }
-  const size_t pl = o.policy_name ? std::strlen(o.policy_name) : 0;
-  const size_t sl = o.source_address ? std::strlen(o.source_address) : 0;
-  const size_t dl = o.destination_address ? std::strlen(o.destination_address) : 0;
+  const l7m_access_log_opts o = l7m::log_norm_opts(opts);
+  HostConsts c;
+  l7m::log_const_fields(o, &c.head, &c.policy, &c.addrs);
+  c.head_len = c.head.size();
+  c.policy_len = c.policy.size();
+  c.addrs_len = c.addrs.size();
+  c.local_identity = o.local_identity;
+  const HostSrc src{arena};
   uint64_t total = 0;
   const bool write = out != nullptr;
-  Pb pb, kv;
   for (size_t i = 0; i < n; ++i) {
     entry_offs[i] = total;
-    HttpView v;
-    if (!http_rec(arena, arena_bytes, offs[i], &v) || verdicts[i] <= L7M_VERDICT_PARSE_ERROR) continue;
-    const bool denied = verdicts[i] == L7M_VERDICT_DENY;
-    const bool ingress = (v.flags & L7M_HTTP_F_INGRESS) != 0;
-    pb.b.clear();
-    // field order as SerializeToString emits it (accesslog.proto numbers)
-    pb.u64(1, o.timestamp_ns);
-    pb.u64(2, o.http_protocol);
-    pb.u64(3, denied ? 2u : 0u);  // EntryType Denied (encodeHeaders of the 403) / Request
-    pb.bytes(4, o.policy_name, pl);
-    // 5 cilium_rule_ref: not set by this reference's filter
-    pb.u64(6, ingress ? v.remote_id : o.local_identity);  // SocketMarkOption identity_ (the source)
-    pb.bytes(7, o.source_address, sl);
-    pb.bytes(8, o.destination_address, dl);
-    // headers in request order; x-forwarded-proto -> scheme (accesslog.cc:103-131)
-    const uint8_t* scheme = nullptr;
-    uint32_t scheme_len = 0;
-    std::string hdrs;
-    const uint8_t* q = v.names;
-    for (uint32_t j = 0; j < v.nhdr; ++j) {
-      uint32_t e;
-      std::memcpy(&e, v.dir + 4 * j, 4);
-      const uint32_t nl = e & 0xffffu, vl = e >> 16;
-      if (nl == 17 && std::memcmp(q, "x-forwarded-proto", 17) == 0) {
-        scheme = q + nl;
-        scheme_len = vl;
-      } else {
-        kv.b.clear();
-        kv.bytes(1, reinterpret_cast<const char*>(q), nl);
-        kv.bytes(2, reinterpret_cast<const char*>(q + nl), vl);
-        Pb f;
-        f.key(14, 2);
-        f.varint(kv.b.size());
-        hdrs += f.b;
-        hdrs += kv.b;
-      }
-      q += nl + vl;
+    l7m::LogView v;
+    if (!l7m::log_wanted(verdicts[i], L7M_LOG_FORWARDED | L7M_LOG_DENIED) ||
+        !l7m::log_view(src, arena_bytes, offs[i], v))
+      continue;
+    const uint64_t size = l7m::log_measure(src, v, verdicts[i], c);
+    if (write && total + size <= cap) {
+      HostSink k{out + total};
+      l7m::log_emit(src, v, verdicts[i], c, k);
     }
-    pb.bytes(9, reinterpret_cast<const char*>(scheme), scheme_len);
-    if (v.flags & L7M_HTTP_F_AUTHORITY) pb.bytes(10, reinterpret_cast<const char*>(v.authority), v.alen);
-    if (v.flags & L7M_HTTP_F_PATH) pb.bytes(11, reinterpret_cast<const char*>(v.path), v.plen);
-    if (v.flags & L7M_HTTP_F_METHOD) pb.bytes(12, reinterpret_cast<const char*>(v.method), v.mlen);
-    pb.u64(13, denied ? 403u : 0u);  // responseCode of the local reply
-    pb.b += hdrs;
-    pb.u64(15, ingress ? 1u : 0u);
-    if (write && total + pb.b.size() <= cap) std::memcpy(out + total, pb.b.data(), pb.b.size());
-    total += pb.b.size();
+    total += size;
   }
   if (n) entry_offs[n] = total;
   return write && total > cap ? static_cast<int64_t>(L7M_ENOMEM) : static_cast<int64_t>(total);
@@ -576,6 +550,23 @@ struct l7m_proxy_stats_table {
   std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, l7m_proxy_stats> m;
 };
 
+namespace l7m {
+
+void proxy_stats_merge_http(l7m_proxy_stats_table* t, const uint64_t* counters) {
+  std::lock_guard<std::mutex> g(t->mu);
+  for (uint32_t row = 0; row < kStatsRows; ++row) {
+    const uint64_t* c = counters + static_cast<size_t>(row) * kStatsClasses;
+    if (!(c[0] | c[1] | c[2])) continue;
+    l7m_proxy_stats& s = t->m[std::make_tuple(static_cast<uint32_t>(L7M_PROTO_HTTP), row & 0xffffu, row >> 16, 1u)];
+    s.received += c[0] + c[1] + c[2];
+    s.forwarded += c[0];
+    s.denied += c[1];
+    s.error += c[2];
+  }
+}
+
+}  // namespace l7m
+
 extern "C" {
 
 l7m_proxy_stats_table* l7m_proxy_stats_table_create(void) { return new (std::nothrow) l7m_proxy_stats_table(); }
@@ -593,8 +584,8 @@ int l7m_proxy_stats_update(l7m_proxy_stats_table* t, uint32_t proto, const uint8
     if (proto == L7M_PROTO_HTTP) {
       // from the access-log entry: DestinationEndpoint.Port and the entry's
       // direction (pkg/envoy/accesslog_server.go:165-169)
-      HttpView v;
-      if (!http_rec(arena, arena_bytes, offs[i], &v)) {
+      l7m::LogView v;
+      if (!l7m::log_view(HostSrc{arena}, arena_bytes, offs[i], v)) {
         p = port;
       } else {
         p = v.dport;

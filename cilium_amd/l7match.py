@@ -56,6 +56,8 @@ HTTP_REC_FIXED = 20
 # status of a request head the wire decoder refuses (L7M_WIRE_E*)
 WIRE_EINCOMPLETE, WIRE_EBADLINE, WIRE_EBADHEADER, WIRE_EDUPHOST, WIRE_ETOOMANY, WIRE_ETOOLONG = -1, -2, -3, -4, -5, -6
 F_METHOD, F_PATH, F_AUTHORITY, F_INGRESS = 1, 2, 4, 8
+# l7m_http_access_log_device `select`: which requests get an entry (0 = both)
+LOG_FORWARDED, LOG_DENIED = 1, 2
 
 # Every symbol include/l7match.h declares (checked by
 # tests/test_http_cpu.py::test_library_exports_every_header_symbol).
@@ -75,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "l7m_multi_eval_device",
     "l7m_http_wire_arena_bound", "l7m_http_wire_decode", "l7m_http_wire_decode_device", "l7m_http_wire_encode",
     "l7m_batcher_eval_http_wire", "l7m_ruleset_http_lean",
+    "l7m_http_access_log_device", "l7m_proxy_stats_update_device",
 )
 
 
@@ -261,6 +264,9 @@ def _load() -> ctypes.CDLL:
     lib.l7m_proxy_stats_get.restype = sz
     lib.l7m_http_access_log.argtypes = [P, sz, P, sz, P, ctypes.POINTER(_AccessLogOpts), P, sz, P]
     lib.l7m_http_access_log.restype = ctypes.c_int64
+    lib.l7m_http_access_log_device.argtypes = [P, sz, P, sz, P, ctypes.POINTER(_AccessLogOpts), ctypes.c_uint32, P, sz,
+                                               P, P, P]
+    lib.l7m_proxy_stats_update_device.argtypes = [P, ctypes.c_uint32, P, sz, P, P, sz, ctypes.c_uint16, ctypes.c_int, P]
     lib.l7m_kafka_access_log.argtypes = [P, sz, P, sz, P, P, sz]
     lib.l7m_kafka_access_log.restype = ctypes.c_int64
     lib.l7m_kafka_api_key_name.argtypes = [ctypes.c_int16, ctypes.c_char_p, sz]
@@ -957,6 +963,13 @@ def kafka_deny_response(request: bytes) -> bytes:
     return buf.raw[:need.value]
 
 
+def _dev_ptr(x):
+    """A device pointer argument: None, an int, or a torch tensor."""
+    if x is None:
+        return None
+    return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+
+
 def proxy_stats(verdicts: np.ndarray) -> dict:
     """Per-endpoint proxy counters of a batch of verdicts (l7m_proxy_stats_add)."""
     v = np.ascontiguousarray(verdicts, dtype=np.int32)
@@ -991,6 +1004,16 @@ class ProxyStatsTable:
         if rc != L7M_OK:
             raise L7Error(rc, "l7m_proxy_stats_update failed")
 
+    def update_device(self, proto: int, d_arena, arena_bytes: int, d_offsets, d_verdicts, n: int,
+                      port: int = 0, ingress: bool = True, stream=None) -> None:
+        """l7m_proxy_stats_update_device: an HTTP batch in device memory (ints
+        or torch tensors).  Counts on `stream` (int handle), then SYNCHRONISES
+        it and merges into this host table."""
+        rc = _lib.l7m_proxy_stats_update_device(self._h, proto, _dev_ptr(d_arena), arena_bytes, _dev_ptr(d_offsets),
+                                                _dev_ptr(d_verdicts), n, port, 1 if ingress else 0, stream)
+        if rc != L7M_OK:
+            raise L7Error(rc, "l7m_proxy_stats_update_device failed")
+
     def entries(self) -> dict:
         n = _lib.l7m_proxy_stats_get(self._h, None, 0)
         arr = (_ProxyStatsEntry * max(1, n))()
@@ -1023,6 +1046,24 @@ def http_access_log(arena: np.ndarray, offsets: np.ndarray, verdicts: np.ndarray
         raise L7Error(L7M_EINVAL, "l7m_http_access_log size changed")
     raw = buf.raw
     return [raw[int(eo[i]):int(eo[i + 1])] for i in range(n)]
+
+
+def http_access_log_device(d_arena, arena_bytes: int, d_offsets, n: int, d_verdicts, d_out, cap: int, d_entry_offs,
+                           d_total, stream=None, select: int = 0, policy_name: str = "", timestamp_ns: int = 0,
+                           http_protocol: int = 1, local_identity: int = 0, source_address: str = None,
+                           destination_address: str = None) -> None:
+    """l7m_http_access_log_device: device pointers (ints or torch tensors) ->
+    enqueue on `stream` (int handle), no synchronisation.  select: 0 (both) or
+    LOG_FORWARDED | LOG_DENIED.  d_entry_offs: n + 1 uint64, d_total: one
+    uint64; when it ends up above cap (d_out None with cap 0 is the sizing
+    call), d_out was not written.  The options are those of http_access_log."""
+    o = _AccessLogOpts(ctypes.sizeof(_AccessLogOpts), http_protocol, timestamp_ns, _b(policy_name), local_identity,
+                       0, _b(source_address), _b(destination_address))
+    rc = _lib.l7m_http_access_log_device(_dev_ptr(d_arena), arena_bytes, _dev_ptr(d_offsets), n, _dev_ptr(d_verdicts),
+                                         ctypes.byref(o), select, _dev_ptr(d_out), cap, _dev_ptr(d_entry_offs),
+                                         _dev_ptr(d_total), stream)
+    if rc != L7M_OK:
+        raise L7Error(rc, "l7m_http_access_log_device failed")
 
 
 def kafka_access_log(arena: np.ndarray, offsets: np.ndarray, verdicts: np.ndarray) -> List[dict]:

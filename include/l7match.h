@@ -628,6 +628,22 @@ int l7m_proxy_stats_update(l7m_proxy_stats_table* t, uint32_t proto, const uint8
                            const uint64_t* rec_offsets, const int32_t* verdicts, size_t n, uint16_t port,
                            int ingress);
 size_t l7m_proxy_stats_get(l7m_proxy_stats_table* t, l7m_proxy_stats_entry* out, size_t cap);
+/* l7m_proxy_stats_update for an HTTP batch in device memory (d_arena with the
+ * contract of l7m_eval_device, d_rec_offsets u64[n], d_verdicts i32[n]): a
+ * kernel on hip_stream counts the requests per (port, direction, verdict
+ * class) -- the record's own port and direction when it validates, the
+ * caller's `port` and `ingress` when it does not, every request counted --
+ * and the counters are added to the table, which lives on the host: the call
+ * SYNCHRONISES hip_stream before it merges and returns.  proto must be
+ * L7M_PROTO_HTTP.  L7M_PROTO_KAFKA answers L7M_EINVAL: a Kafka batch is keyed
+ * by the caller's own (port, ingress), not by its records, so a device path
+ * would amount to copying four bytes of verdict per request; use
+ * l7m_proxy_stats_update.  L7M_EINVAL also for a NULL table, NULL inputs with
+ * n > 0 and a d_arena that is not 16-byte aligned; L7M_EDEVICE without a
+ * device. */
+int l7m_proxy_stats_update_device(l7m_proxy_stats_table* t, uint32_t proto, const void* d_arena, size_t arena_bytes,
+                                  const void* d_rec_offsets, const void* d_verdicts, size_t n, uint16_t port,
+                                  int ingress, void* hip_stream);
 
 /* ---- access-log records of a decided batch ---------------------------------
  * HTTP: the HttpLogEntry protobuf (envoy/cilium/accesslog.proto) Envoy's
@@ -656,6 +672,35 @@ typedef struct {
 int64_t l7m_http_access_log(const uint8_t* arena, size_t arena_bytes, const uint64_t* rec_offsets, size_t n,
                             const int32_t* verdicts, const l7m_access_log_opts* opts, uint8_t* out, size_t cap,
                             uint64_t* entry_offs);
+/* The same entries for a batch that stayed in device memory, where
+ * l7m_http_wire_decode_device / l7m_eval_device left it: three kernels
+ * (measure, scan, emit) enqueued on hip_stream; the call does not synchronise
+ * and the host reads no byte of the batch.  Every pointer but opts is device
+ * memory.  d_arena as for l7m_eval_device: 16-byte aligned and readable up to
+ * arena_bytes rounded up to 16 (L7M_EINVAL otherwise); record offsets are
+ * arbitrary, as for the host function.  d_out needs no alignment.
+ *   select      L7M_LOG_FORWARDED | L7M_LOG_DENIED: which requests get an
+ *               entry; 0 means both.  A request outside the selection gets an
+ *               empty entry, like a record that does not parse.
+ *   d_entry_offs  u64[n + 1]: entry i is d_out[entry_offs[i], entry_offs[i+1]),
+ *               entries back to back, byte for byte those of the host function
+ *   d_total     one u64: entry_offs[n]
+ * When the total exceeds cap (d_out == NULL with cap == 0 is the sizing call)
+ * no byte of d_out is written, d_entry_offs and *d_total are complete all the
+ * same; otherwise no byte of d_out at or past the total is written.  (The host
+ * function instead writes the entries that still fit.)
+ * opts is host memory, read during the call with the struct_size rule above;
+ * its constant fields travel to the kernels as arguments, so policy_name,
+ * source_address and destination_address are limited to 255 bytes each here
+ * (L7M_EINVAL; the host function takes any length).  L7M_EINVAL also for a
+ * NULL d_total, NULL inputs or d_entry_offs with n > 0, cap > 0 without d_out,
+ * bits in select other than the two; L7M_EDEVICE without a device. */
+#define L7M_LOG_FORWARDED 1u   /* entries for allowed requests  */
+#define L7M_LOG_DENIED    2u   /* entries for denied requests   */
+int l7m_http_access_log_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
+                               const void* d_verdicts, const l7m_access_log_opts* opts /* host */,
+                               uint32_t select /* 0 = both */, void* d_out, size_t cap,
+                               void* d_entry_offs /* u64[n+1] */, void* d_total /* u64 */, void* hip_stream);
 /* Kafka: the proxy's log records (kafkaLogRecord.log, pkg/proxy/kafka.go
  * :168-230; LogRecordKafka, pkg/proxy/accesslog/record.go:220-241): one
  * record per topic of GetTopics() (none for requests without topics), verdict
