@@ -703,6 +703,37 @@ int l7m_http_access_log_device(const void* d_arena, size_t arena_bytes, const vo
   return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
 }
 
+int l7m_kafka_deny_responses_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
+                                    const void* d_verdicts, void* d_out, size_t cap, void* d_resp_offs,
+                                    void* d_total, void* hip_stream) {
+  if (!d_total || (n && (!d_arena || !d_rec_offsets || !d_verdicts || !d_resp_offs)) || (cap && !d_out))
+    return L7M_EINVAL;
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return L7M_EINVAL;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
+  const hipError_t e = launch_kafka_side(
+      false, static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets), n,
+      static_cast<const int32_t*>(d_verdicts), 0, static_cast<uint8_t*>(d_out), cap,
+      static_cast<uint64_t*>(d_resp_offs), static_cast<uint64_t*>(d_total), static_cast<hipStream_t>(hip_stream));
+  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+}
+
+int l7m_kafka_access_log_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
+                                const void* d_verdicts, uint32_t select, void* d_out, size_t cap, void* d_first,
+                                void* d_total, void* hip_stream) {
+  if (!d_total || (n && (!d_arena || !d_rec_offsets || !d_verdicts || !d_first)) || (cap && !d_out) ||
+      (select & ~(L7M_LOG_FORWARDED | L7M_LOG_DENIED)))
+    return L7M_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(d_arena) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 7)) return L7M_EINVAL;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
+  const hipError_t e = launch_kafka_side(
+      true, static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets), n,
+      static_cast<const int32_t*>(d_verdicts), select, static_cast<uint8_t*>(d_out), cap,
+      static_cast<uint64_t*>(d_first), static_cast<uint64_t*>(d_total), static_cast<hipStream_t>(hip_stream));
+  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+}
+
 int l7m_proxy_stats_update_device(l7m_proxy_stats_table* t, uint32_t proto, const void* d_arena, size_t arena_bytes,
                                   const void* d_rec_offsets, const void* d_verdicts, size_t n, uint16_t port,
                                   int ingress, void* hip_stream) {

@@ -136,6 +136,15 @@ hipError_t launch_http_stats(const uint8_t* arena, uint64_t arena_bytes, const u
                              const int32_t* verdicts, uint64_t n, uint32_t caller_row, uint64_t* host_counters,
                              hipStream_t stream);
 
+// Deny responses (log = false: sizes and cap in bytes, `select` unused) or
+// per-topic log records (log = true: in records) of a decided Kafka batch
+// (l7m_kafka_side.hip): measure pass, scan and emit pass enqueued on `stream`.
+// out_offs (u64[n + 1]) and *total are always written; nothing of `out` is
+// when the total exceeds cap.
+hipError_t launch_kafka_side(bool log, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n,
+                             const int32_t* verdicts, uint32_t select, uint8_t* out, uint64_t cap,
+                             uint64_t* out_offs, uint64_t* total, hipStream_t stream);
+
 // Mailbox of a resident evaluator (l7m_kafka.hip kafka_resident_kernel),
 // in pinned, device-mapped host memory.  The host fills slot seq %
 // kResidentSlots, then raises post_seq to seq (release); the workgroup

@@ -174,3 +174,5 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
 // The HTTP/1.x wire decoder's kernels and launch_http_wire: same code object.
 #include "l7m_http_wire.hip"
 #include "l7m_http_log.hip"
+// The Kafka deny-response and log-record encoders (LogOutSink, the tile scan).
+#include "l7m_kafka_side.hip"

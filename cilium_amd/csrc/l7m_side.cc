@@ -28,208 +28,10 @@
 #include "../../include/l7match.h"
 #include "l7m_http_log.h"
 #include "l7m_internal.h"
+#include "l7m_kafka_side.h"
 #include "program.h"
 
 namespace {
-
-// Big-endian request reader with optiopay's sticky-error semantics.
-struct Rd {
-  const uint8_t* p;
-  size_t n, pos = 0;
-  bool err = false;
-  uint64_t be(size_t k) {
-    if (err || n - pos < k) {
-      err = true;
-      pos = n;
-      return 0;
-    }
-    uint64_t v = 0;
-    for (size_t i = 0; i < k; ++i) v = v << 8 | p[pos + i];
-    pos += k;
-    return v;
-  }
-  int16_t i16() { return static_cast<int16_t>(be(2)); }
-  int32_t i32() { return static_cast<int32_t>(be(4)); }
-  std::string str(size_t* at = nullptr) {  // DecodeString: int16 length, < 1 -> ""
-    const int16_t k = i16();
-    if (at) *at = pos;
-    if (err || k < 1) return "";
-    if (n - pos < static_cast<size_t>(k)) {
-      err = true;
-      pos = n;
-      return "";
-    }
-    std::string s(reinterpret_cast<const char*>(p + pos), static_cast<size_t>(k));
-    pos += static_cast<size_t>(k);
-    return s;
-  }
-  void skip(size_t k) {
-    if (err || n - pos < k) {
-      err = true;
-      pos = n;
-      return;
-    }
-    pos += k;
-  }
-  int32_t arraylen() {
-    const int32_t v = i32();
-    if (v < 0 || v > l7m::kKafkaMaxParseBuf) err = true;
-    return err ? 0 : v;
-  }
-  void bytes() {  // DecodeBytes, value discarded
-    const int32_t k = i32();
-    if (err || k < 1) return;
-    if (k > l7m::kKafkaMaxParseBuf || n - pos < static_cast<size_t>(k)) {
-      err = true;
-      pos = n;
-      return;
-    }
-    pos += static_cast<size_t>(k);
-  }
-};
-
-struct Wr {
-  std::vector<uint8_t> b;
-  void be(uint64_t v, int k) {
-    for (int i = k - 1; i >= 0; --i) b.push_back(static_cast<uint8_t>(v >> (8 * i)));
-  }
-  void i8(int v) { be(static_cast<uint8_t>(v), 1); }
-  void i16(int v) { be(static_cast<uint16_t>(v), 2); }
-  void i32(int64_t v) { be(static_cast<uint32_t>(v), 4); }
-  void i64(int64_t v) { be(static_cast<uint64_t>(v), 8); }
-  void str(const std::string& s) {  // Encode(string): uint16 length + bytes
-    i16(static_cast<int>(s.size()));
-    b.insert(b.end(), s.begin(), s.end());
-  }
-};
-
-constexpr int kErrTopicAuthorizationFailed = 29;  // vendor/.../proto/errors.go:37
-// time.Time{}.UnixNano() / int64(time.Millisecond) on a 64-bit Go: the zero
-// Time's nanoseconds overflow int64 and wrap (OffsetResp v>=1 TimeStamp).
-constexpr int64_t kZeroTimeMillis = -6795364578871LL;
-
-// Bytes readMessageSet (messages.go:357-483) consumes from its LimitReader:
-// it can stop inside the set (a bad CRC, attributes 3), and the request's
-// next partition is then read from there.  Only called for requests whose
-// verdict is a deny, i.e. whose decode succeeded.
-size_t message_set_consumed(const uint8_t* p, size_t avail, int32_t size, int16_t version) {
-  const size_t lim = avail < static_cast<size_t>(size) ? avail : static_cast<size_t>(size);
-  size_t pos = 0;
-  for (;;) {
-    if (lim - pos < 12) return lim;  // offset / size: short reads consume the rest
-    pos += 8;
-    const int32_t msz = static_cast<int32_t>(static_cast<uint32_t>(p[pos]) << 24 | static_cast<uint32_t>(p[pos + 1]) << 16 |
-                                             static_cast<uint32_t>(p[pos + 2]) << 8 | p[pos + 3]);
-    pos += 4;
-    if (msz <= 0) return pos;
-    if (lim - pos < static_cast<size_t>(msz)) return lim;
-    const uint8_t* m = p + pos;
-    pos += static_cast<size_t>(msz);
-    if (msz <= 4) return pos;
-    uint32_t c = 0xffffffffu;
-    for (int32_t i = 4; i < msz; ++i) {
-      c ^= m[i];
-      for (int k = 0; k < 8; ++k) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-    }
-    const uint32_t crc = static_cast<uint32_t>(m[0]) << 24 | static_cast<uint32_t>(m[1]) << 16 |
-                         static_cast<uint32_t>(m[2]) << 8 | m[3];
-    if ((c ^ 0xffffffffu) != crc) return pos;
-    const size_t ap = 5;  // crc, magic
-    if (msz > static_cast<int32_t>(ap) && (m[ap] & 3) == 3) return pos;
-    (void)version;
-  }
-}
-
-struct TopicParts {
-  std::string name;
-  size_t at = 0;  // offset of the name's bytes in the request
-  std::vector<int32_t> parts;
-};
-
-// What GetTopics / CreateResponse need of a request whose decode succeeded
-// (pkg/kafka/request.go:88-108,158-182 over optiopay's per-kind readers).
-struct KReq {
-  int16_t kind = 0, version = 0;
-  int32_t corr = 0;
-  std::vector<TopicParts> topics;
-};
-
-// L7M_OK, L7M_EINVAL (decode error), L7M_EUNSUPPORTED (request == nil: a kind
-// ReadRequest leaves untyped, request.go:204-220).
-int read_kafka(const uint8_t* req, size_t len, KReq* q) {
-  Rd r{req, len};
-  r.i32();  // size
-  q->kind = r.i16();
-  q->version = r.i16();
-  q->corr = r.i32();
-  if (r.err) return L7M_EINVAL;
-  const int16_t version = q->version;
-  auto partitions = [&](TopicParts& t, size_t fixed, bool produce, bool commit) {
-    const int32_t np = r.arraylen();
-    for (int32_t k = 0; k < np && !r.err; ++k) {
-      t.parts.push_back(r.i32());
-      if (produce) {
-        const int32_t sz = r.i32();
-        if (r.err) break;
-        if (sz < 0 || sz > l7m::kKafkaMaxParseBuf) r.err = true;
-        else r.pos += message_set_consumed(r.p + r.pos, r.n - r.pos, sz, version);
-      } else if (commit) {
-        r.skip(8 + (version == 1 ? 8 : 0));
-        r.str();
-      } else {
-        r.skip(fixed);
-      }
-    }
-  };
-  auto read_topics = [&](size_t fixed, bool produce, bool commit, bool names_only) {
-    const int32_t nt = r.arraylen();
-    for (int32_t k = 0; k < nt && !r.err; ++k) {
-      TopicParts t;
-      t.name = r.str(&t.at);
-      if (!names_only) partitions(t, fixed, produce, commit);
-      q->topics.push_back(std::move(t));
-    }
-  };
-  r.str();  // ClientID
-  switch (q->kind) {
-    case 0:  // ReadProduceReq
-      if (version >= 3) r.str();
-      r.skip(6);
-      read_topics(0, true, false, false);
-      break;
-    case 1:  // ReadFetchReq
-      r.skip(12 + (version >= 3 ? 4 : 0) + (version >= 4 ? 1 : 0));
-      read_topics(12 + (version >= 5 ? 8 : 0), false, false, false);
-      break;
-    case 2:  // ReadOffsetReq
-      r.skip(4 + (version >= 2 ? 1 : 0));
-      read_topics(8 + (version == 0 ? 4 : 0), false, false, false);
-      break;
-    case 3:  // ReadMetadataReq
-      read_topics(0, false, false, true);
-      break;
-    case 8:  // ReadOffsetCommitReq
-      r.str();
-      if (version >= 1) {
-        r.skip(4);
-        r.str();
-      }
-      if (version >= 2) r.skip(8);
-      read_topics(0, false, true, false);
-      break;
-    case 9:  // ReadOffsetFetchReq
-      r.str();
-      read_topics(0, false, false, false);
-      break;
-    case 10:  // ReadConsumerMetadataReq
-      r.str();
-      if (version >= 1) r.skip(1);
-      break;
-    default:
-      return L7M_EUNSUPPORTED;
-  }
-  return r.err ? L7M_EINVAL : L7M_OK;
-}
 
 // Protobuf wire writer (proto3: default-valued fields are omitted).
 struct Pb {
@@ -263,17 +65,6 @@ const char* const kApiKeyNames[] = {  // api.KafkaReverseAPIKeyMap (pkg/policy/a
     "addpartitionstotxn", "addoffsetstotxn", "endtxn", "writetxnmarkers", "txnoffsetcommit",
     "describeacls", "createacls", "deleteacls", "describeconfigs", "alterconfigs"};
 
-// Kafka record at offs[i]: the size-prefixed request; false if it does not fit.
-bool kafka_rec(const uint8_t* arena, size_t arena_bytes, uint64_t o, size_t* len) {
-  if (o > arena_bytes || arena_bytes - o < 4) return false;
-  const uint8_t* p = arena + o;
-  const uint64_t sz = static_cast<uint64_t>(p[0]) << 24 | static_cast<uint64_t>(p[1]) << 16 |
-                      static_cast<uint64_t>(p[2]) << 8 | p[3];
-  if (sz > arena_bytes - o - 4) return false;
-  *len = static_cast<size_t>(sz + 4);
-  return true;
-}
-
 // The host's instantiation of l7m_http_log.h: the arena in host memory, an
 // entry written where the caller's buffer has room for it.
 struct HostSrc {
@@ -296,6 +87,37 @@ struct HostConsts {  // fields 1-2, 4, 7-8 of every entry of a call
 };
 
 using l7m::flow_verdict;
+
+// The host's instantiation of l7m_kafka_side.h: a request is walked once for
+// what it takes (the response's size, the number of topics) and, when that
+// succeeded and the caller's buffer has room, once more for the output.
+// L7M_OK, L7M_EINVAL or L7M_EUNSUPPORTED as kafka_walk answers.
+int kafka_resp_size(const HostSrc& src, uint64_t off, uint64_t len, uint64_t* size) {
+  l7m::KafkaHead h;
+  l7m::KafkaRespSize m;
+  const int rc = l7m::kafka_walk(src, off, len, l7m::KafkaCrcBitwise{}, h, m);
+  *size = m.bytes;
+  return rc;
+}
+void kafka_resp_emit(const HostSrc& src, uint64_t off, uint64_t len, uint64_t size, uint8_t* out) {
+  l7m::KafkaHead h;
+  l7m::KafkaRespEmit<HostSrc, HostSink> e(src, HostSink{out}, size);
+  l7m::kafka_walk(src, off, len, l7m::KafkaCrcBitwise{}, h, e);
+}
+// The log records of request `request` into out[k, cap), counting in k.
+struct HostLogEmit {
+  l7m_kafka_log_record* out;
+  size_t cap;
+  uint64_t k, request;
+  int32_t verdict;
+  void topics(const l7m::KafkaHead&, int32_t) {}
+  void topic(const l7m::KafkaHead& h, uint64_t at, uint32_t nl, int32_t) {
+    if (k < cap) l7m::kafka_log_fill(out[k], request, verdict, h, at, nl);
+    ++k;
+  }
+  void partition(const l7m::KafkaHead&, int32_t) {}
+  void end(const l7m::KafkaHead&) {}
+};
 
 }  // namespace
 
@@ -344,120 +166,33 @@ size_t l7m_http_deny_body(const char* configured, char* out, size_t cap) {
 
 int l7m_kafka_deny_response(const uint8_t* req, size_t len, uint8_t* out, size_t cap, size_t* out_len) {
   if (!req || !out_len) return L7M_EINVAL;
-  KReq q;
-  const int rc = read_kafka(req, len, &q);
+  const HostSrc src{req};
+  uint64_t size = 0;
+  const int rc = kafka_resp_size(src, 0, len, &size);
   if (rc != L7M_OK) return rc;
-  const int16_t version = q.version;
-  const std::vector<TopicParts>& topics = q.topics;
-  Wr w;
-  w.i32(0);  // size placeholder
-  w.i32(q.corr);
-  switch (q.kind) {
-    case 0:  // ProduceResp.Bytes (messages.go:1697)
-      w.i32(static_cast<int64_t>(topics.size()));
-      for (const auto& t : topics) {
-        w.str(t.name);
-        w.i32(static_cast<int64_t>(t.parts.size()));
-        for (int32_t id : t.parts) {
-          w.i32(id);
-          w.i16(kErrTopicAuthorizationFailed);
-          w.i64(0);                     // Offset
-          if (version >= 2) w.i64(0);   // LogAppendTime
-        }
-      }
-      if (version >= 1) w.i32(0);  // ThrottleTime
-      break;
-    case 1:  // FetchResp.Bytes (messages.go:896)
-      if (version >= 1) w.i32(0);  // ThrottleTime
-      w.i32(static_cast<int64_t>(topics.size()));
-      for (const auto& t : topics) {
-        w.str(t.name);
-        w.i32(static_cast<int64_t>(t.parts.size()));
-        for (int32_t id : t.parts) {
-          w.i32(id);
-          w.i16(kErrTopicAuthorizationFailed);
-          w.i64(0);  // TipOffset
-          if (version >= 4) {
-            w.i64(0);                    // LastStableOffset
-            if (version >= 5) w.i64(0);  // LogStartOffset
-            w.i32(0);                    // AbortedTransactions
-          }
-          w.i32(0);  // message set size: no messages
-        }
-      }
-      break;
-    case 2:  // OffsetResp.Bytes (messages.go:1956)
-      if (version >= 2) w.i32(0);  // ThrottleTime
-      w.i32(static_cast<int64_t>(topics.size()));
-      for (const auto& t : topics) {
-        w.str(t.name);
-        w.i32(static_cast<int64_t>(t.parts.size()));
-        for (int32_t id : t.parts) {
-          w.i32(id);
-          w.i16(kErrTopicAuthorizationFailed);
-          if (version >= 1) w.i64(kZeroTimeMillis);
-          w.i32(0);  // Offsets
-        }
-      }
-      break;
-    case 3:  // MetadataResp.Bytes (messages.go:595)
-      if (version >= 3) w.i32(0);  // ThrottleTime
-      w.i32(0);                    // Brokers
-      if (version >= 2) w.str("");  // ClusterID
-      if (version >= 1) w.i32(0);   // ControllerID
-      w.i32(static_cast<int64_t>(topics.size()));
-      for (const auto& t : topics) {
-        w.i16(kErrTopicAuthorizationFailed);
-        w.str(t.name);
-        if (version >= 1) w.i8(0);  // IsInternal
-        w.i32(0);                   // Partitions
-      }
-      break;
-    case 8:  // OffsetCommitResp.Bytes (messages.go:1327)
-      if (version >= 3) w.i32(0);
-      w.i32(static_cast<int64_t>(topics.size()));
-      for (const auto& t : topics) {
-        w.str(t.name);
-        w.i32(static_cast<int64_t>(t.parts.size()));
-        for (int32_t id : t.parts) {
-          w.i32(id);
-          w.i16(kErrTopicAuthorizationFailed);
-        }
-      }
-      break;
-    case 9:  // OffsetFetchResp.Bytes (messages.go:1512)
-      if (version >= 3) w.i32(0);
-      w.i32(static_cast<int64_t>(topics.size()));
-      for (const auto& t : topics) {
-        w.str(t.name);
-        w.i32(static_cast<int64_t>(t.parts.size()));
-        for (int32_t id : t.parts) {
-          w.i32(id);
-          w.i64(0);    // Offset
-          w.str("");   // Metadata
-          w.i16(kErrTopicAuthorizationFailed);
-        }
-      }
-      if (version >= 2) w.i16(0);  // resp.Err: left nil by createOffsetFetchResponse
-      break;
-    case 10:  // ConsumerMetadataResp.Bytes (messages.go:1102)
-      if (version >= 1) w.i32(0);  // ThrottleTime
-      w.i16(kErrTopicAuthorizationFailed);
-      if (version >= 1) w.str("");  // ErrMsg
-      w.i32(0);                     // CoordinatorID
-      w.str("");                    // CoordinatorHost
-      w.i32(0);                     // CoordinatorPort
-      break;
-  }
-  const uint32_t sz = static_cast<uint32_t>(w.b.size() - 4);
-  w.b[0] = static_cast<uint8_t>(sz >> 24);
-  w.b[1] = static_cast<uint8_t>(sz >> 16);
-  w.b[2] = static_cast<uint8_t>(sz >> 8);
-  w.b[3] = static_cast<uint8_t>(sz);
-  *out_len = w.b.size();
-  if (!out || cap < w.b.size()) return L7M_ENOMEM;
-  std::memcpy(out, w.b.data(), w.b.size());
+  *out_len = static_cast<size_t>(size);
+  if (!out || cap < size) return L7M_ENOMEM;
+  kafka_resp_emit(src, 0, len, size, out);
   return L7M_OK;
+}
+
+int64_t l7m_kafka_deny_responses(const uint8_t* arena, size_t arena_bytes, const uint64_t* offs, size_t n,
+                                 const int32_t* verdicts, uint8_t* out, size_t cap, uint64_t* resp_offs) {
+  if (n && (!arena || !offs || !verdicts || !resp_offs)) return L7M_EINVAL;
+  const HostSrc src{arena};
+  uint64_t total = 0;
+  const bool write = out != nullptr;
+  for (size_t i = 0; i < n; ++i) {
+    resp_offs[i] = total;
+    uint64_t len = 0, size = 0;
+    if (verdicts[i] != L7M_VERDICT_DENY || !l7m::kafka_rec(src, arena_bytes, offs[i], &len) ||
+        kafka_resp_size(src, offs[i], len, &size) != L7M_OK)
+      continue;
+    if (write && total + size <= cap) kafka_resp_emit(src, offs[i], len, size, out + total);
+    total += size;
+  }
+  if (n) resp_offs[n] = total;
+  return write && total > cap ? static_cast<int64_t>(L7M_ENOMEM) : static_cast<int64_t>(total);
 }
 
 size_t l7m_kafka_api_key_name(int16_t key, char* out, size_t cap) {
@@ -507,35 +242,24 @@ int64_t l7m_http_access_log(const uint8_t* arena, size_t arena_bytes, const uint
 int64_t l7m_kafka_access_log(const uint8_t* arena, size_t arena_bytes, const uint64_t* offs, size_t n,
                              const int32_t* verdicts, l7m_kafka_log_record* out, size_t cap) {
   if (n && (!arena || !offs || !verdicts)) return L7M_EINVAL;
+  const HostSrc src{arena};
   uint64_t k = 0;
   for (size_t i = 0; i < n; ++i) {
     const int32_t vd = verdicts[i];
     // ReadRequest failed: the connection is closed, nothing is logged
     // (pkg/proxy/kafka.go:349-354); -3 (a codec limit of this library) too.
-    if (vd == L7M_VERDICT_PARSE_ERROR || vd == L7M_VERDICT_UNSUPPORTED) continue;
-    size_t len;
-    if (!kafka_rec(arena, arena_bytes, offs[i], &len)) continue;
-    KReq q;
-    const int rc = read_kafka(arena + offs[i], len, &q);
-    if (rc != L7M_OK) continue;  // request == nil: GetTopics() is nil, no records
-    // allowed: Forwarded / ErrNone; denied: CreateResponse succeeds for every
-    // typed request -> Denied / ErrTopicAuthorizationFailed (kafka.go:240-262,296)
-    const uint32_t fv = flow_verdict(vd);
-    for (const auto& t : q.topics) {  // one record per topic (kafka.go:207-211)
-      if (out && k < cap) {
-        l7m_kafka_log_record& r = out[k];
-        r.request = i;
-        r.verdict = fv;
-        r.error_code = fv == 1 ? kErrTopicAuthorizationFailed : 0;
-        r.api_key = q.kind;
-        r.api_version = q.version;
-        r.correlation_id = q.corr;
-        r.topic_off = offs[i] + t.at;
-        r.topic_len = static_cast<uint32_t>(t.name.size());
-        r.pad = 0;
-      }
-      ++k;
+    if (!l7m::kafka_log_wanted(vd, 0)) continue;
+    uint64_t len = 0;
+    if (!l7m::kafka_rec(src, arena_bytes, offs[i], &len)) continue;
+    l7m::KafkaHead h;
+    l7m::KafkaTopicCount c;
+    // request == nil: GetTopics() is nil, no records
+    if (l7m::kafka_walk(src, offs[i], len, l7m::KafkaCrcBitwise{}, h, c) != L7M_OK) continue;
+    if (out && k < cap) {  // one record per topic (kafka.go:207-211)
+      HostLogEmit e{out, cap, k, i, vd};
+      l7m::kafka_walk(src, offs[i], len, l7m::KafkaCrcBitwise{}, h, e);
     }
+    k += c.topics_seen;
   }
   return out && k > cap ? static_cast<int64_t>(L7M_ENOMEM) : static_cast<int64_t>(k);
 }
@@ -602,9 +326,12 @@ int l7m_proxy_stats_update(l7m_proxy_stats_table* t, uint32_t proto, const uint8
       // which fails for the kinds ReadRequest leaves untyped (request == nil,
       // request.go:174-175): the record is then logged as VerdictError
       // (kafka.go:246-252)
-      size_t len = 0;
-      KReq q;
-      if (kafka_rec(arena, arena_bytes, offs[i], &len) && read_kafka(arena + offs[i], len, &q) == L7M_EUNSUPPORTED)
+      uint64_t len = 0;
+      l7m::KafkaHead h;
+      l7m::KafkaTopicCount c;
+      const HostSrc src{arena};
+      if (l7m::kafka_rec(src, arena_bytes, offs[i], &len) &&
+          l7m::kafka_walk(src, offs[i], len, l7m::KafkaCrcBitwise{}, h, c) == L7M_EUNSUPPORTED)
         fv = 2;
     }
     if (p == 0 && proto == L7M_PROTO_KAFKA) continue;

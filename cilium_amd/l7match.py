@@ -78,6 +78,7 @@ EXPORTED_SYMBOLS = (
     "l7m_http_wire_arena_bound", "l7m_http_wire_decode", "l7m_http_wire_decode_device", "l7m_http_wire_encode",
     "l7m_batcher_eval_http_wire", "l7m_ruleset_http_lean",
     "l7m_http_access_log_device", "l7m_proxy_stats_update_device",
+    "l7m_kafka_deny_responses", "l7m_kafka_deny_responses_device", "l7m_kafka_access_log_device",
 )
 
 
@@ -190,6 +191,12 @@ class _KafkaLogRecord(ctypes.Structure):
                 ("topic_off", ctypes.c_uint64), ("topic_len", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
+# l7m_kafka_log_record as a numpy record (what kafka_access_log_device leaves in d_out)
+KAFKA_LOG_RECORD_DTYPE = np.dtype([("request", "<u8"), ("verdict", "<u4"), ("error_code", "<i4"), ("api_key", "<i2"),
+                                   ("api_version", "<i2"), ("correlation_id", "<i4"), ("topic_off", "<u8"),
+                                   ("topic_len", "<u4"), ("pad", "<u4")])
+
+
 class _ProxyStats(ctypes.Structure):
     _fields_ = [("received", ctypes.c_uint64), ("forwarded", ctypes.c_uint64), ("denied", ctypes.c_uint64),
                 ("error", ctypes.c_uint64)]
@@ -269,6 +276,10 @@ def _load() -> ctypes.CDLL:
     lib.l7m_proxy_stats_update_device.argtypes = [P, ctypes.c_uint32, P, sz, P, P, sz, ctypes.c_uint16, ctypes.c_int, P]
     lib.l7m_kafka_access_log.argtypes = [P, sz, P, sz, P, P, sz]
     lib.l7m_kafka_access_log.restype = ctypes.c_int64
+    lib.l7m_kafka_deny_responses.argtypes = [P, sz, P, sz, P, P, sz, P]
+    lib.l7m_kafka_deny_responses.restype = ctypes.c_int64
+    lib.l7m_kafka_deny_responses_device.argtypes = [P, sz, P, sz, P, P, sz, P, P, P]
+    lib.l7m_kafka_access_log_device.argtypes = [P, sz, P, sz, P, ctypes.c_uint32, P, sz, P, P, P]
     lib.l7m_kafka_api_key_name.argtypes = [ctypes.c_int16, ctypes.c_char_p, sz]
     lib.l7m_kafka_api_key_name.restype = sz
     lib.l7m_ruleset_rule_origin.argtypes = [P, ctypes.c_uint32, ctypes.POINTER(_RuleOrigin)]
@@ -963,11 +974,57 @@ def kafka_deny_response(request: bytes) -> bytes:
     return buf.raw[:need.value]
 
 
+def kafka_deny_responses(arena: np.ndarray, offsets: np.ndarray, verdicts: np.ndarray) -> List[bytes]:
+    """The deny response of every request of a decided batch (l7m_kafka_deny_responses): b"" for a
+    request that is not denied or has no response."""
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    v = np.ascontiguousarray(verdicts, dtype=np.int32)
+    n = v.shape[0]
+    ro = np.zeros(n + 1, dtype=np.uint64)
+    need = _lib.l7m_kafka_deny_responses(arena.ctypes.data, arena.nbytes, offsets.ctypes.data, n, v.ctypes.data,
+                                         None, 0, ro.ctypes.data)
+    if need < 0:
+        raise L7Error(int(need), "l7m_kafka_deny_responses failed")
+    buf = ctypes.create_string_buffer(max(1, need))
+    got = _lib.l7m_kafka_deny_responses(arena.ctypes.data, arena.nbytes, offsets.ctypes.data, n, v.ctypes.data,
+                                        buf, need, ro.ctypes.data)
+    if got != need:
+        raise L7Error(L7M_EINVAL, "l7m_kafka_deny_responses size changed")
+    raw = buf.raw
+    return [raw[int(ro[i]):int(ro[i + 1])] for i in range(n)]
+
+
 def _dev_ptr(x):
     """A device pointer argument: None, an int, or a torch tensor."""
     if x is None:
         return None
     return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+
+
+def kafka_deny_responses_device(d_arena, arena_bytes: int, d_offsets, n: int, d_verdicts, d_out, cap: int,
+                                d_resp_offs, d_total, stream=None) -> None:
+    """l7m_kafka_deny_responses_device: device pointers (ints or torch tensors) -> enqueue on `stream`
+    (int handle), no synchronisation.  d_resp_offs: n + 1 uint64, d_total: one uint64; when it ends up
+    above cap (d_out None with cap 0 is the sizing call), d_out was not written."""
+    rc = _lib.l7m_kafka_deny_responses_device(_dev_ptr(d_arena), arena_bytes, _dev_ptr(d_offsets), n,
+                                              _dev_ptr(d_verdicts), _dev_ptr(d_out), cap, _dev_ptr(d_resp_offs),
+                                              _dev_ptr(d_total), stream)
+    if rc != L7M_OK:
+        raise L7Error(rc, "l7m_kafka_deny_responses_device failed")
+
+
+def kafka_access_log_device(d_arena, arena_bytes: int, d_offsets, n: int, d_verdicts, d_out, cap: int, d_first,
+                            d_total, stream=None, select: int = 0) -> None:
+    """l7m_kafka_access_log_device: as kafka_deny_responses_device, for the per-topic log records.
+    d_out: room for `cap` records of KAFKA_LOG_RECORD_DTYPE (8-byte aligned), d_first: n + 1 uint64
+    (request i's records are d_out[first[i]:first[i + 1]]), d_total: the number of records.  select: 0
+    (every record) or LOG_FORWARDED | LOG_DENIED."""
+    rc = _lib.l7m_kafka_access_log_device(_dev_ptr(d_arena), arena_bytes, _dev_ptr(d_offsets), n,
+                                          _dev_ptr(d_verdicts), select, _dev_ptr(d_out), cap, _dev_ptr(d_first),
+                                          _dev_ptr(d_total), stream)
+    if rc != L7M_OK:
+        raise L7Error(rc, "l7m_kafka_access_log_device failed")
 
 
 def proxy_stats(verdicts: np.ndarray) -> dict:

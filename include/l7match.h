@@ -723,6 +723,51 @@ typedef struct {
 int64_t l7m_kafka_access_log(const uint8_t* arena, size_t arena_bytes, const uint64_t* rec_offsets, size_t n,
                              const int32_t* verdicts, l7m_kafka_log_record* out, size_t cap);
 size_t l7m_kafka_api_key_name(int16_t api_key, char* out, size_t cap);
+/* l7m_kafka_deny_response for a decided batch: responses written back to back
+ * into out, resp_offs[i] .. resp_offs[i+1] is request i's response (n + 1
+ * entries).  Request i gets the bytes l7m_kafka_deny_response gives for its
+ * record when verdicts[i] is L7M_VERDICT_DENY, the record (the size-prefixed
+ * request at rec_offsets[i]) lies inside the arena and that function answers
+ * L7M_OK; an empty response otherwise (an allowed request, a parse error, a
+ * kind ReadRequest leaves untyped, a record that does not decode).  Returns
+ * the total size (out == NULL: the size needed; L7M_ENOMEM when cap is too
+ * small, the responses that still fit written and resp_offs complete).
+ * L7M_EINVAL for NULL inputs or resp_offs with n > 0. */
+int64_t l7m_kafka_deny_responses(const uint8_t* arena, size_t arena_bytes, const uint64_t* rec_offsets, size_t n,
+                                 const int32_t* verdicts, uint8_t* out, size_t cap, uint64_t* resp_offs /* n+1 */);
+/* The two for a batch that stayed in device memory, where l7m_eval_device
+ * left it: three kernels each (measure, scan, emit) enqueued on hip_stream;
+ * the calls do not synchronise and the host reads no byte of the batch.  Every
+ * pointer is device memory.  d_arena as for l7m_eval_device: 16-byte aligned
+ * and readable up to arena_bytes rounded up to 16 (L7M_EINVAL otherwise);
+ * record offsets are arbitrary, unaligned ones included, as for the host
+ * functions.
+ * l7m_kafka_deny_responses_device: d_resp_offs u64[n + 1] and the bytes of
+ *   d_out (any alignment) are those of l7m_kafka_deny_responses; d_total one
+ *   u64, resp_offs[n].
+ * l7m_kafka_access_log_device: d_out l7m_kafka_log_record[cap], 8-byte aligned
+ *   (L7M_EINVAL otherwise); cap and *d_total count records; d_first u64[n + 1],
+ *   request i's records are d_out[first[i], first[i+1]).  The records are, in
+ *   order and byte for byte (pad = 0 included), those l7m_kafka_access_log
+ *   fills; with select = L7M_LOG_FORWARDED | L7M_LOG_DENIED (their HTTP
+ *   meaning) only those of that array whose `verdict` is in the selection, 0
+ *   means all of them.  topic_off is an arena offset, valid on either side.
+ * When the total exceeds cap (d_out == NULL with cap == 0 is the sizing call)
+ * nothing of d_out is written, the offsets and *d_total are complete all the
+ * same; otherwise no byte or record of d_out at or past the total is written.
+ * (The host functions instead write what still fits.)  L7M_EINVAL also for a
+ * NULL d_total, NULL inputs or offsets with n > 0, cap > 0 without d_out, bits
+ * in select other than the two; L7M_EDEVICE without a device.  Proxy
+ * statistics of a Kafka batch have no device twin: see
+ * l7m_proxy_stats_update_device. */
+int l7m_kafka_deny_responses_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
+                                    const void* d_verdicts, void* d_out, size_t cap,
+                                    void* d_resp_offs /* u64[n+1] */, void* d_total /* u64 */, void* hip_stream);
+int l7m_kafka_access_log_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
+                                const void* d_verdicts, uint32_t select /* 0 = all */,
+                                void* d_out /* l7m_kafka_log_record[cap] */, size_t cap,
+                                void* d_first /* u64[n+1]: index of request i's first record */,
+                                void* d_total /* u64: number of records */, void* hip_stream);
 
 /* Pinned host memory helpers (cgo may not retain Go pointers across calls).
  * l7m_eval on an arena in pinned, device-mapped memory whose padded range
