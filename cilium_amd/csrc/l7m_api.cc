@@ -670,6 +670,46 @@ int l7m_http_wire_decode_device(const void* d_wire, size_t wire_bytes, const voi
   return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
 }
 
+int l7m_http_stream_frame_device(const void* d_wire, size_t wire_bytes, const void* d_conn_offs, size_t n_conns,
+                                 const void* d_conn_meta, void* d_head_offs, void* d_head_conn, void* d_head_meta,
+                                 size_t cap_heads, void* d_conn_status, void* d_conn_consumed, void* d_n_heads,
+                                 void* hip_stream) {
+  if (!d_n_heads || !d_conn_offs || (n_conns && (!d_conn_status || !d_conn_consumed)) || (wire_bytes && !d_wire) ||
+      (cap_heads && (!d_head_offs || !d_head_conn)) || n_conns > 0xffffffffull)
+    return L7M_EINVAL;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
+  const hipError_t e = launch_http_stream_frame(
+      static_cast<const uint8_t*>(d_wire), wire_bytes, static_cast<const uint64_t*>(d_conn_offs), n_conns,
+      static_cast<const l7m_http_wire_meta*>(d_conn_meta), static_cast<uint64_t*>(d_head_offs),
+      static_cast<uint32_t*>(d_head_conn), static_cast<l7m_http_wire_meta*>(d_head_meta), cap_heads,
+      static_cast<int32_t*>(d_conn_status), static_cast<uint64_t*>(d_conn_consumed),
+      static_cast<uint64_t*>(d_n_heads), static_cast<hipStream_t>(hip_stream));
+  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+}
+
+int l7m_kafka_stream_frame_device(const void* d_wire, size_t wire_bytes, const void* d_conn_offs, size_t n_conns,
+                                  const void* d_conn_identity, void* d_arena, size_t cap_bytes, void* d_rec_offsets,
+                                  void* d_rec_conn, void* d_src_identities, size_t cap_recs, void* d_conn_status,
+                                  void* d_conn_consumed, void* d_n_recs, void* d_arena_bytes, void* hip_stream) {
+  if (!d_n_recs || !d_arena_bytes || !d_conn_offs || (n_conns && (!d_conn_status || !d_conn_consumed)) ||
+      (wire_bytes && !d_wire) || (cap_recs && (!d_rec_offsets || !d_rec_conn)) || (cap_bytes && !d_arena) ||
+      n_conns > 0xffffffffull)
+    return L7M_EINVAL;
+  // what l7m_eval_device asks of its arena; the copy kernel stores 16-byte units
+  if (reinterpret_cast<uintptr_t>(d_arena) & 15) return L7M_EINVAL;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
+  const hipError_t e = launch_kafka_stream_frame(
+      static_cast<const uint8_t*>(d_wire), wire_bytes, static_cast<const uint64_t*>(d_conn_offs), n_conns,
+      static_cast<const uint32_t*>(d_conn_identity), static_cast<uint8_t*>(d_arena), cap_bytes,
+      static_cast<uint64_t*>(d_rec_offsets), static_cast<uint32_t*>(d_rec_conn),
+      static_cast<uint32_t*>(d_src_identities), cap_recs, static_cast<int32_t*>(d_conn_status),
+      static_cast<uint64_t*>(d_conn_consumed), static_cast<uint64_t*>(d_n_recs),
+      static_cast<uint64_t*>(d_arena_bytes), static_cast<hipStream_t>(hip_stream));
+  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+}
+
 int l7m_http_access_log_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
                                const void* d_verdicts, const l7m_access_log_opts* opts, uint32_t select, void* d_out,
                                size_t cap, void* d_entry_offs, void* d_total, void* hip_stream) {

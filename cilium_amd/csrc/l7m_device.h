@@ -145,6 +145,22 @@ hipError_t launch_kafka_side(bool log, const uint8_t* arena, uint64_t arena_byte
                              const int32_t* verdicts, uint32_t select, uint8_t* out, uint64_t cap,
                              uint64_t* out_offs, uint64_t* total, hipStream_t stream);
 
+// Connection byte streams -> head slices for the wire decoder, or Kafka
+// records in a dword-aligned arena (l7m_stream_frame.hip): count pass, scan
+// and emit pass (Kafka: two scans and a copy kernel) enqueued on `stream`.
+// Statuses, consumed bytes and the totals (u64, device) are always written;
+// nothing per head or record, and nothing of `arena`, when a total exceeds its
+// capacity.
+hipError_t launch_http_stream_frame(const uint8_t* wire, uint64_t wire_bytes, const uint64_t* conn_offs, uint64_t n,
+                                    const l7m_http_wire_meta* conn_meta, uint64_t* head_offs, uint32_t* head_conn,
+                                    l7m_http_wire_meta* head_meta, uint64_t cap, int32_t* conn_status,
+                                    uint64_t* conn_consumed, uint64_t* total, hipStream_t stream);
+hipError_t launch_kafka_stream_frame(const uint8_t* wire, uint64_t wire_bytes, const uint64_t* conn_offs, uint64_t n,
+                                     const uint32_t* conn_identity, uint8_t* arena, uint64_t cap_bytes,
+                                     uint64_t* rec_offsets, uint32_t* rec_conn, uint32_t* src_identities,
+                                     uint64_t cap_recs, int32_t* conn_status, uint64_t* conn_consumed,
+                                     uint64_t* n_recs, uint64_t* arena_bytes, hipStream_t stream);
+
 // Mailbox of a resident evaluator (l7m_kafka.hip kafka_resident_kernel),
 // in pinned, device-mapped host memory.  The host fills slot seq %
 // kResidentSlots, then raises post_seq to seq (release); the workgroup

@@ -176,3 +176,5 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
 #include "l7m_http_log.hip"
 // The Kafka deny-response and log-record encoders (LogOutSink, the tile scan).
 #include "l7m_kafka_side.hip"
+// Connection byte streams -> head slices / Kafka records (the tile scan).
+#include "l7m_stream_frame.hip"

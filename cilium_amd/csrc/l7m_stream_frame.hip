@@ -1,0 +1,320 @@
+// l7m_stream_frame.hip — connection byte streams -> head slices / Kafka
+// records on the device (include/l7match.h l7m_http_stream_frame_device,
+// l7m_kafka_stream_frame_device; the framing rules in l7m_stream_frame.h,
+// shared with the host functions of stream_frame.cc).
+//
+// Work is sequential inside a connection and independent across connections:
+// a workgroup owns a tile of kTileThreads consecutive connections, one per
+// lane.
+//   count: each lane walks its connection; status, consumed bytes, its number
+//          of slices (Kafka: and of padded arena bytes), the tile's sums
+//   scan:  exclusive sum of the tile sums (l7m_tile_scan.h), the totals
+//   emit:  when the totals fit the capacities each lane walks its connection
+//          again and writes its slices at tile base + sum inside the tile + k
+//   copy:  (Kafka) balanced over the arena, not over records: a thread takes
+//          16-byte units, finds the record of each by binary search in
+//          rec_offsets and reads the unaligned source as aligned dwords joined
+//          with v_alignbyte
+// The walks read the wire from global memory byte by byte, as the Kafka side
+// effects do (l7m_kafka_side.hip): a connection has no size limit, bodies and
+// chunk data are skipped by their size, and neighbouring lanes read
+// neighbouring connections.  A lane reads inside its connection's range
+// clamped to the wire only, whatever the offsets hold.
+//
+// Compiled as part of l7m_kernels.hip's translation unit (included at its end).
+#include <hip/hip_runtime.h>
+
+#include "l7m_device.h"
+#include "l7m_stream_frame.h"
+#include "l7m_tile_scan.h"
+
+namespace l7m {
+namespace {
+
+struct SfGlobalSrc {
+  const uint8_t* p;
+  __device__ uint8_t at(uint64_t i) const { return p[i]; }
+};
+
+// Connection c of the tile, clamped to the wire: wire[lo, hi).
+struct ConnRange {
+  uint64_t lo, hi;
+};
+
+__device__ __forceinline__ ConnRange conn_range(const uint64_t* conn_offs, uint64_t c, uint64_t n, uint64_t wire_bytes) {
+  ConnRange r{0, 0};
+  if (c < n) {
+    const uint64_t a = conn_offs[c], b = conn_offs[c + 1];
+    r.lo = a < wire_bytes ? a : wire_bytes;
+    r.hi = b < wire_bytes ? b : wire_bytes;
+    if (r.hi < r.lo) r.hi = r.lo;
+  }
+  return r;
+}
+
+__global__ __launch_bounds__(kTileThreads) void stream_http_count(const uint8_t* wire, uint64_t wire_bytes,
+                                                                  const uint64_t* conn_offs, uint64_t n,
+                                                                  int32_t* conn_status, uint64_t* conn_consumed,
+                                                                  uint32_t* counts, uint64_t* tile_sums) {
+  __shared__ uint64_t tmp[kTileThreads];
+  const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
+  uint64_t cnt = 0;
+  if (c < n) {
+    const ConnRange r = conn_range(conn_offs, c, n, wire_bytes);
+    uint64_t used = 0;
+    const int32_t st = http_stream_walk(SfGlobalSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t) { ++cnt; });
+    conn_status[c] = st;
+    conn_consumed[c] = used;
+    counts[c] = static_cast<uint32_t>(cnt);  // <= (hi - lo) / 16 + 1
+  }
+  const uint64_t incl = block_inclusive(cnt, tmp);
+  if (threadIdx.x == kTileThreads - 1) tile_sums[blockIdx.x] = incl;
+}
+
+__global__ __launch_bounds__(kTileThreads) void stream_http_emit(const uint8_t* wire, uint64_t wire_bytes,
+                                                                 const uint64_t* conn_offs, uint64_t n,
+                                                                 const l7m_http_wire_meta* conn_meta,
+                                                                 uint64_t* head_offs, uint32_t* head_conn,
+                                                                 l7m_http_wire_meta* head_meta, uint64_t cap,
+                                                                 const uint32_t* counts, const uint64_t* tile_base,
+                                                                 const uint64_t* total) {
+  __shared__ uint64_t tmp[kTileThreads];
+  const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
+  const uint64_t cnt = c < n ? counts[c] : 0;
+  const uint64_t base = tile_base[blockIdx.x] + block_inclusive(cnt, tmp) - cnt;
+  const uint64_t all = *total;
+  if (all > cap || !head_offs) return;  // uniform: the per-head arrays stay untouched
+  if (c >= n) return;
+  const ConnRange r = conn_range(conn_offs, c, n, wire_bytes);
+  if (c + 1 == n) head_offs[all] = r.hi;
+  if (!cnt) return;
+  l7m_http_wire_meta m{0, 0, 0, 1, {0, 0, 0}};  // no metadata: zeros, ingress
+  if (conn_meta) m = conn_meta[c];
+  uint64_t used = 0, k = 0;
+  http_stream_walk(SfGlobalSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t start) {
+    if (k < cnt) {  // never more than the count pass counted
+      head_offs[base + k] = r.lo + start;
+      head_conn[base + k] = static_cast<uint32_t>(c);
+      if (head_meta) head_meta[base + k] = m;
+    }
+    ++k;
+  });
+}
+
+// A record's source in the wire: its offset in the low 40 bits, the frame's
+// bytes above them (a frame is under 2^23 bytes).
+constexpr uint32_t kSrcShift = 40;
+
+__global__ __launch_bounds__(kTileThreads) void stream_kafka_count(const uint8_t* wire, uint64_t wire_bytes,
+                                                                   const uint64_t* conn_offs, uint64_t n,
+                                                                   int32_t* conn_status, uint64_t* conn_consumed,
+                                                                   uint32_t* counts, uint64_t* sizes,
+                                                                   uint64_t* tile_recs, uint64_t* tile_bytes) {
+  __shared__ uint64_t tmp[kTileThreads];
+  const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
+  uint64_t cnt = 0, bytes = 0;
+  if (c < n) {
+    const ConnRange r = conn_range(conn_offs, c, n, wire_bytes);
+    uint64_t used = 0;
+    const int32_t st = kafka_stream_walk(SfGlobalSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t, uint64_t frame) {
+      ++cnt;
+      bytes += stream_padded(frame);
+    });
+    conn_status[c] = st;
+    conn_consumed[c] = used;
+    counts[c] = static_cast<uint32_t>(cnt);  // <= (hi - lo) / 12
+    sizes[c] = bytes;
+  }
+  const uint64_t incl = block_inclusive(cnt, tmp);
+  if (threadIdx.x == kTileThreads - 1) tile_recs[blockIdx.x] = incl;
+  __syncthreads();
+  const uint64_t incl_b = block_inclusive(bytes, tmp);
+  if (threadIdx.x == kTileThreads - 1) tile_bytes[blockIdx.x] = incl_b;
+}
+
+__global__ __launch_bounds__(kTileThreads) void stream_kafka_emit(
+    const uint8_t* wire, uint64_t wire_bytes, const uint64_t* conn_offs, uint64_t n, const uint32_t* conn_identity,
+    uint64_t* rec_offsets, uint32_t* rec_conn, uint32_t* src_identities, uint64_t cap_recs, uint64_t cap_bytes,
+    const uint32_t* counts, const uint64_t* sizes, const uint64_t* tile_recs, const uint64_t* tile_bytes,
+    uint64_t* src /* src_cap */, uint64_t src_cap, const uint64_t* n_recs, const uint64_t* arena_bytes) {
+  __shared__ uint64_t tmp[kTileThreads];
+  const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
+  const uint64_t cnt = c < n ? counts[c] : 0;
+  const uint64_t bytes = c < n ? sizes[c] : 0;
+  const uint64_t base = tile_recs[blockIdx.x] + block_inclusive(cnt, tmp) - cnt;
+  __syncthreads();
+  uint64_t off = tile_bytes[blockIdx.x] + block_inclusive(bytes, tmp) - bytes;
+  if (*n_recs > cap_recs || *n_recs > src_cap || *arena_bytes > cap_bytes) return;  // uniform: nothing per record
+  if (!cnt) return;
+  const ConnRange r = conn_range(conn_offs, c, n, wire_bytes);
+  const uint32_t id = conn_identity ? conn_identity[c] : 0u;
+  uint64_t used = 0, k = 0;
+  kafka_stream_walk(SfGlobalSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t start, uint64_t frame) {
+    if (k < cnt) {  // never more than the count pass counted
+      rec_offsets[base + k] = off;
+      rec_conn[base + k] = static_cast<uint32_t>(c);
+      if (src_identities) src_identities[base + k] = id;
+      src[base + k] = (r.lo + start) | frame << kSrcShift;
+      off += stream_padded(frame);
+    }
+    ++k;
+  });
+}
+
+// The aligned dword at address g of the wire [w0, w1); bytes outside it read as zero.
+__device__ __forceinline__ uint32_t wire_dword(uint64_t g, uint64_t w0, uint64_t w1) {
+  if (g >= w0 && g + 4 <= w1) return *reinterpret_cast<const uint32_t*>(g);
+  uint32_t v = 0;
+  for (uint32_t b = 0; b < 4; ++b)
+    if (g + b >= w0 && g + b < w1) v |= static_cast<uint32_t>(*reinterpret_cast<const uint8_t*>(g + b)) << (8u * b);
+  return v;
+}
+
+// Arena dword at offset q (a multiple of four) of a record whose frame is
+// wire[s, s + len): the source bytes, zero past the frame.
+__device__ __forceinline__ uint32_t frame_dword(uint64_t w0, uint64_t w1, uint64_t s, uint64_t len, uint64_t q) {
+  const uint64_t a = w0 + s + q;
+  const uint32_t sh = static_cast<uint32_t>(a & 3u);
+  const uint64_t g = a & ~3ull;
+  const uint32_t lo = wire_dword(g, w0, w1);
+  const uint32_t hi = sh ? wire_dword(g + 4, w0, w1) : 0u;
+  uint32_t v = __builtin_amdgcn_alignbyte(hi, lo, sh);
+  const uint64_t left = len - q;  // >= 1
+  if (left < 4) v &= (1u << (8u * static_cast<uint32_t>(left))) - 1u;
+  return v;
+}
+
+__global__ __launch_bounds__(kTileThreads) void stream_kafka_copy(const uint8_t* wire, uint64_t wire_bytes,
+                                                                  uint8_t* arena, uint64_t cap_recs,
+                                                                  uint64_t cap_bytes, const uint64_t* rec_offsets,
+                                                                  const uint64_t* src, uint64_t src_cap,
+                                                                  const uint64_t* n_recs, const uint64_t* arena_bytes) {
+  const uint64_t n = *n_recs, total = *arena_bytes;  // a multiple of four
+  if (n > cap_recs || n > src_cap || total > cap_bytes || n == 0) return;
+  const uint64_t w0 = reinterpret_cast<uint64_t>(wire), w1 = w0 + wire_bytes;
+  const uint64_t units = (total + 15) >> 4;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kTileThreads;
+  for (uint64_t u = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x; u < units; u += stride) {
+    const uint64_t d0 = u << 4;
+    // the record that holds arena byte d0: the last one with rec_offsets[r] <= d0
+    uint64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+      const uint64_t mid = (lo + hi) >> 1;
+      if (rec_offsets[mid] <= d0) lo = mid;
+      else hi = mid;
+    }
+    uint64_t r = lo, ro = rec_offsets[r];
+    uint64_t rend = r + 1 < n ? rec_offsets[r + 1] : total;
+    uint64_t sl = src[r];
+    uint32_t w[4] = {0, 0, 0, 0};
+    const uint32_t nd = total - d0 >= 16 ? 4u : static_cast<uint32_t>((total - d0) >> 2);
+    const uint64_t s0 = sl & ((1ull << kSrcShift) - 1), len0 = sl >> kSrcShift;
+    const uint64_t a0 = w0 + s0 + (d0 - ro);
+    if (nd == 4 && d0 + 16 <= ro + len0 && (a0 & ~3ull) >= w0 && (a0 & ~3ull) + 20 <= w1) {
+      // the whole unit inside one frame and its source window inside the wire: five aligned dwords
+      const uint32_t* g = reinterpret_cast<const uint32_t*>(a0 & ~3ull);
+      const uint32_t sh = static_cast<uint32_t>(a0 & 3u);
+      const uint32_t x0 = g[0], x1 = g[1], x2 = g[2], x3 = g[3], x4 = sh ? g[4] : 0u;
+      w[0] = __builtin_amdgcn_alignbyte(x1, x0, sh);
+      w[1] = __builtin_amdgcn_alignbyte(x2, x1, sh);
+      w[2] = __builtin_amdgcn_alignbyte(x3, x2, sh);
+      w[3] = __builtin_amdgcn_alignbyte(x4, x3, sh);
+    } else {
+      for (uint32_t j = 0; j < nd; ++j) {
+        const uint64_t d = d0 + 4u * j;
+        while (d >= rend) {  // records are at least 12 bytes: at most two steps per unit
+          ++r;
+          ro = rend;
+          rend = r + 1 < n ? rec_offsets[r + 1] : total;
+          sl = src[r];
+        }
+        const uint64_t len = sl >> kSrcShift, q = d - ro;
+        w[j] = q < len ? frame_dword(w0, w1, sl & ((1ull << kSrcShift) - 1), len, q) : 0u;
+      }
+    }
+    if (nd == 4) {
+      *reinterpret_cast<uint4*>(arena + d0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+      for (uint32_t j = 0; j < nd; ++j) *reinterpret_cast<uint32_t*>(arena + d0 + 4u * j) = w[j];
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t launch_http_stream_frame(const uint8_t* wire, uint64_t wire_bytes, const uint64_t* conn_offs, uint64_t n,
+                                    const l7m_http_wire_meta* conn_meta, uint64_t* head_offs, uint32_t* head_conn,
+                                    l7m_http_wire_meta* head_meta, uint64_t cap, int32_t* conn_status,
+                                    uint64_t* conn_consumed, uint64_t* total, hipStream_t stream) {
+  if (n == 0) {
+    hipError_t e = hipMemsetAsync(total, 0, sizeof(uint64_t), stream);
+    if (e == hipSuccess && head_offs)
+      e = hipMemcpyAsync(head_offs, conn_offs, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream);
+    return e;
+  }
+  const uint64_t tiles = (n + kTileThreads - 1) / kTileThreads;
+  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
+  void* scratch = nullptr;
+  hipError_t e = scratch_alloc_async(&scratch, tiles * sizeof(uint64_t) + n * sizeof(uint32_t), stream);
+  if (e != hipSuccess) return e;
+  uint64_t* tile_sums = static_cast<uint64_t*>(scratch);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(tile_sums + tiles);
+  const dim3 grid(static_cast<uint32_t>(tiles)), block(kTileThreads);
+  stream_http_count<<<grid, block, 0, stream>>>(wire, wire_bytes, conn_offs, n, conn_status, conn_consumed, counts,
+                                                tile_sums);
+  http_wire_scan_tiles<<<dim3(1), dim3(kScanThreads), 0, stream>>>(tile_sums, tiles, total);
+  stream_http_emit<<<grid, block, 0, stream>>>(wire, wire_bytes, conn_offs, n, conn_meta, head_offs, head_conn,
+                                               head_meta, cap, counts, tile_sums, total);
+  e = hipGetLastError();
+  const hipError_t f = hipFreeAsync(scratch, stream);
+  return e != hipSuccess ? e : f;
+}
+
+hipError_t launch_kafka_stream_frame(const uint8_t* wire, uint64_t wire_bytes, const uint64_t* conn_offs, uint64_t n,
+                                     const uint32_t* conn_identity, uint8_t* arena, uint64_t cap_bytes,
+                                     uint64_t* rec_offsets, uint32_t* rec_conn, uint32_t* src_identities,
+                                     uint64_t cap_recs, int32_t* conn_status, uint64_t* conn_consumed,
+                                     uint64_t* n_recs, uint64_t* arena_bytes, hipStream_t stream) {
+  if (n == 0) {
+    hipError_t e = hipMemsetAsync(n_recs, 0, sizeof(uint64_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(arena_bytes, 0, sizeof(uint64_t), stream);
+    return e;
+  }
+  if (wire_bytes >> kSrcShift) return hipErrorInvalidValue;
+  const uint64_t tiles = (n + kTileThreads - 1) / kTileThreads;
+  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
+  // what ascending offsets can yield, and no more than the caller's arrays hold
+  const uint64_t bound = wire_bytes / 12;
+  const uint64_t src_cap = cap_recs < bound ? cap_recs : bound;
+  void* scratch = nullptr;
+  hipError_t e = scratch_alloc_async(
+      &scratch, (2 * tiles + n + src_cap) * sizeof(uint64_t) + n * sizeof(uint32_t), stream);
+  if (e != hipSuccess) return e;
+  uint64_t* tile_recs = static_cast<uint64_t*>(scratch);
+  uint64_t* tile_bytes = tile_recs + tiles;
+  uint64_t* sizes = tile_bytes + tiles;
+  uint64_t* src = sizes + n;
+  uint32_t* counts = reinterpret_cast<uint32_t*>(src + src_cap);
+  const dim3 grid(static_cast<uint32_t>(tiles)), block(kTileThreads);
+  stream_kafka_count<<<grid, block, 0, stream>>>(wire, wire_bytes, conn_offs, n, conn_status, conn_consumed, counts,
+                                                 sizes, tile_recs, tile_bytes);
+  http_wire_scan_tiles<<<dim3(1), dim3(kScanThreads), 0, stream>>>(tile_recs, tiles, n_recs);
+  http_wire_scan_tiles<<<dim3(1), dim3(kScanThreads), 0, stream>>>(tile_bytes, tiles, arena_bytes);
+  stream_kafka_emit<<<grid, block, 0, stream>>>(wire, wire_bytes, conn_offs, n, conn_identity, rec_offsets, rec_conn,
+                                                src_identities, cap_recs, cap_bytes, counts, sizes, tile_recs,
+                                                tile_bytes, src, src_cap, n_recs, arena_bytes);
+  // the copy's grid from the capacity (the total is on the device): 16-byte units, at most 2048 workgroups
+  const uint64_t abound = wire_bytes + wire_bytes / 4;
+  const uint64_t units = ((cap_bytes < abound ? cap_bytes : abound) + 15) >> 4;
+  if (units && src_cap) {
+    uint64_t blocks = (units + kTileThreads - 1) / kTileThreads;
+    if (blocks > 2048) blocks = 2048;
+    stream_kafka_copy<<<dim3(static_cast<uint32_t>(blocks)), block, 0, stream>>>(
+        wire, wire_bytes, arena, cap_recs, cap_bytes, rec_offsets, src, src_cap, n_recs, arena_bytes);
+  }
+  e = hipGetLastError();
+  const hipError_t f = hipFreeAsync(scratch, stream);
+  return e != hipSuccess ? e : f;
+}
+
+}  // namespace l7m

@@ -58,6 +58,10 @@ WIRE_EINCOMPLETE, WIRE_EBADLINE, WIRE_EBADHEADER, WIRE_EDUPHOST, WIRE_ETOOMANY, 
 F_METHOD, F_PATH, F_AUTHORITY, F_INGRESS = 1, 2, 4, 8
 # l7m_http_access_log_device `select`: which requests get an entry (0 = both)
 LOG_FORWARDED, LOG_DENIED = 1, 2
+# conn_status of the stream framers (L7M_STREAM_*)
+STREAM_OK, STREAM_TUNNEL = 0, 1
+(STREAM_EBADHEAD, STREAM_EPARTIAL_HEAD, STREAM_EAMBIGUOUS, STREAM_EBADTE, STREAM_EBADLENGTH, STREAM_EBADCHUNK,
+ STREAM_EPARTIAL_BODY, STREAM_EPARTIAL_FRAME, STREAM_EBADSIZE) = -1, -2, -3, -4, -5, -6, -7, -8, -9
 
 # Every symbol include/l7match.h declares (checked by
 # tests/test_http_cpu.py::test_library_exports_every_header_symbol).
@@ -79,6 +83,9 @@ EXPORTED_SYMBOLS = (
     "l7m_batcher_eval_http_wire", "l7m_ruleset_http_lean",
     "l7m_http_access_log_device", "l7m_proxy_stats_update_device",
     "l7m_kafka_deny_responses", "l7m_kafka_deny_responses_device", "l7m_kafka_access_log_device",
+    "l7m_http_stream_heads_bound", "l7m_http_stream_frame", "l7m_http_stream_frame_device",
+    "l7m_kafka_stream_records_bound", "l7m_kafka_stream_arena_bound", "l7m_kafka_stream_frame",
+    "l7m_kafka_stream_frame_device",
 )
 
 
@@ -317,6 +324,17 @@ def _load() -> ctypes.CDLL:
     lib.l7m_http_wire_encode.restype = ctypes.c_int64
     lib.l7m_batcher_eval_http_wire.argtypes = [P, ctypes.c_char_p, sz, ctypes.POINTER(_WireMeta),
                                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    lib.l7m_http_stream_heads_bound.argtypes = [sz, sz]
+    lib.l7m_http_stream_heads_bound.restype = sz
+    lib.l7m_http_stream_frame.argtypes = [P, sz, P, sz, P, P, P, P, sz, P, P, ctypes.POINTER(sz)]
+    lib.l7m_http_stream_frame_device.argtypes = [P, sz, P, sz, P, P, P, P, sz, P, P, P, P]
+    lib.l7m_kafka_stream_records_bound.argtypes = [sz]
+    lib.l7m_kafka_stream_records_bound.restype = sz
+    lib.l7m_kafka_stream_arena_bound.argtypes = [sz]
+    lib.l7m_kafka_stream_arena_bound.restype = sz
+    lib.l7m_kafka_stream_frame.argtypes = [P, sz, P, sz, P, P, sz, P, P, P, sz, P, P, ctypes.POINTER(sz),
+                                           ctypes.POINTER(sz)]
+    lib.l7m_kafka_stream_frame_device.argtypes = [P, sz, P, sz, P, P, sz, P, P, P, sz, P, P, P, P, P]
     return lib
 
 
@@ -611,6 +629,123 @@ def decode_http_wire_device(d_wire, wire_bytes: int, d_head_offs, n: int, d_meta
                                           cap, ptr(d_offsets), ptr(d_status), ptr(d_total), stream)
     if rc != L7M_OK:
         raise L7Error(rc, "l7m_http_wire_decode_device failed")
+
+
+# --------------------------------------------------------------------------
+# Connection byte streams (DESIGN.md "Stream framing")
+# --------------------------------------------------------------------------
+def join_conns(conns) -> Tuple[np.ndarray, np.ndarray]:
+    """Connections back to back: (wire uint8[], conn_offs uint64[n_conns + 1]); a
+    (wire, conn_offs) pair is passed through."""
+    if isinstance(conns, tuple) and len(conns) == 2 and isinstance(conns[1], np.ndarray):
+        return (np.ascontiguousarray(conns[0], dtype=np.uint8), np.ascontiguousarray(conns[1], dtype=np.uint64))
+    return join_heads(list(conns))
+
+
+def http_stream_heads_bound(wire_bytes: int, n_conns: int) -> int:
+    """l7m_http_stream_heads_bound: heads that any n_conns connections in wire_bytes can yield."""
+    return int(_lib.l7m_http_stream_heads_bound(wire_bytes, n_conns))
+
+
+def kafka_stream_bounds(wire_bytes: int) -> Tuple[int, int]:
+    """(l7m_kafka_stream_records_bound, l7m_kafka_stream_arena_bound) of wire_bytes."""
+    return int(_lib.l7m_kafka_stream_records_bound(wire_bytes)), int(_lib.l7m_kafka_stream_arena_bound(wire_bytes))
+
+
+def frame_http_streams(conns, meta=None):
+    """l7m_http_stream_frame (host): conns is a sequence of bytes objects (one per
+    connection) or a (wire, conn_offs) pair; meta None or a WIRE_META_DTYPE array
+    with one entry per connection.  Returns (wire, head_offs, head_conn,
+    head_meta, conn_status, conn_consumed): (wire, head_offs) is what
+    decode_http_wire takes, head_meta (None without meta) goes with it, and
+    conn_status holds a STREAM_* code per connection."""
+    wire, coffs = join_conns(conns)
+    nc = coffs.shape[0] - 1
+    meta = _wire_meta(meta, nc)
+    status = np.zeros(nc, dtype=np.int32)
+    consumed = np.zeros(nc, dtype=np.uint64)
+    n = ctypes.c_size_t(0)
+    rc = _lib.l7m_http_stream_frame(wire.ctypes.data, wire.nbytes, coffs.ctypes.data, nc, None, None, None, None, 0,
+                                    status.ctypes.data, consumed.ctypes.data, ctypes.byref(n))
+    if rc not in (L7M_OK, L7M_ENOMEM):
+        raise L7Error(rc, "l7m_http_stream_frame failed")
+    cap = n.value
+    hoffs = np.zeros(cap + 1, dtype=np.uint64)
+    hconn = np.zeros(cap, dtype=np.uint32)
+    hmeta = None if meta is None else np.zeros(cap, dtype=WIRE_META_DTYPE)
+    rc = _lib.l7m_http_stream_frame(wire.ctypes.data, wire.nbytes, coffs.ctypes.data, nc,
+                                    None if meta is None else meta.ctypes.data, hoffs.ctypes.data,
+                                    hconn.ctypes.data if cap else None,
+                                    None if hmeta is None or not cap else hmeta.ctypes.data, cap,
+                                    status.ctypes.data, consumed.ctypes.data, ctypes.byref(n))
+    if rc != L7M_OK or n.value != cap:
+        raise L7Error(rc, "l7m_http_stream_frame failed")
+    return wire, hoffs, hconn, hmeta, status, consumed
+
+
+def frame_http_streams_device(d_wire, wire_bytes: int, d_conn_offs, n_conns: int, d_conn_meta, d_head_offs,
+                              d_head_conn, d_head_meta, cap_heads: int, d_conn_status, d_conn_consumed, d_n_heads,
+                              stream=None) -> None:
+    """l7m_http_stream_frame_device: device pointers (ints or torch tensors) ->
+    enqueue on `stream` (int handle), no synchronisation.  d_n_heads: one
+    uint64, to be read back before decode_http_wire_device, which takes n from
+    the host; when it ends up above cap_heads the per-head arrays were not written."""
+    rc = _lib.l7m_http_stream_frame_device(_dev_ptr(d_wire), wire_bytes, _dev_ptr(d_conn_offs), n_conns,
+                                           _dev_ptr(d_conn_meta), _dev_ptr(d_head_offs), _dev_ptr(d_head_conn),
+                                           _dev_ptr(d_head_meta), cap_heads, _dev_ptr(d_conn_status),
+                                           _dev_ptr(d_conn_consumed), _dev_ptr(d_n_heads), stream)
+    if rc != L7M_OK:
+        raise L7Error(rc, "l7m_http_stream_frame_device failed")
+
+
+def frame_kafka_streams(conns, identities=None):
+    """l7m_kafka_stream_frame (host): conns as for frame_http_streams; identities
+    None or one uint32 per connection.  Returns (arena, rec_offsets, rec_conn,
+    src_identities, conn_status, conn_consumed): arena and rec_offsets are what
+    RuleSet.eval takes (records dword aligned, pad bytes zero), src_identities
+    (None without identities) what the ids calls take."""
+    wire, coffs = join_conns(conns)
+    nc = coffs.shape[0] - 1
+    ids = None if identities is None else np.ascontiguousarray(identities, dtype=np.uint32)
+    assert ids is None or ids.shape[0] == nc
+    status = np.zeros(nc, dtype=np.int32)
+    consumed = np.zeros(nc, dtype=np.uint64)
+    n, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    rc = _lib.l7m_kafka_stream_frame(wire.ctypes.data, wire.nbytes, coffs.ctypes.data, nc, None, None, 0, None, None,
+                                     None, 0, status.ctypes.data, consumed.ctypes.data, ctypes.byref(n),
+                                     ctypes.byref(nb))
+    if rc not in (L7M_OK, L7M_ENOMEM):
+        raise L7Error(rc, "l7m_kafka_stream_frame failed")
+    cap, cap_bytes = n.value, nb.value
+    arena = np.zeros(max(4, cap_bytes), dtype=np.uint8)
+    offs = np.zeros(cap, dtype=np.uint64)
+    rconn = np.zeros(cap, dtype=np.uint32)
+    sids = None if ids is None else np.zeros(cap, dtype=np.uint32)
+    rc = _lib.l7m_kafka_stream_frame(wire.ctypes.data, wire.nbytes, coffs.ctypes.data, nc,
+                                     None if ids is None else ids.ctypes.data, arena.ctypes.data, cap_bytes,
+                                     offs.ctypes.data if cap else None, rconn.ctypes.data if cap else None,
+                                     None if sids is None or not cap else sids.ctypes.data, cap,
+                                     status.ctypes.data, consumed.ctypes.data, ctypes.byref(n), ctypes.byref(nb))
+    if rc != L7M_OK or n.value != cap or nb.value != cap_bytes:
+        raise L7Error(rc, "l7m_kafka_stream_frame failed")
+    return arena, offs, rconn, sids, status, consumed
+
+
+def frame_kafka_streams_device(d_wire, wire_bytes: int, d_conn_offs, n_conns: int, d_conn_identity, d_arena,
+                               cap_bytes: int, d_rec_offsets, d_rec_conn, d_src_identities, cap_recs: int,
+                               d_conn_status, d_conn_consumed, d_n_recs, d_arena_bytes, stream=None) -> None:
+    """l7m_kafka_stream_frame_device: device pointers (ints or torch tensors) ->
+    enqueue on `stream`, no synchronisation.  d_n_recs, d_arena_bytes: one
+    uint64 each; when either ends up above its capacity neither the per-record
+    arrays nor d_arena (16-byte aligned) were written."""
+    rc = _lib.l7m_kafka_stream_frame_device(_dev_ptr(d_wire), wire_bytes, _dev_ptr(d_conn_offs), n_conns,
+                                            _dev_ptr(d_conn_identity), _dev_ptr(d_arena), cap_bytes,
+                                            _dev_ptr(d_rec_offsets), _dev_ptr(d_rec_conn),
+                                            _dev_ptr(d_src_identities), cap_recs, _dev_ptr(d_conn_status),
+                                            _dev_ptr(d_conn_consumed), _dev_ptr(d_n_recs), _dev_ptr(d_arena_bytes),
+                                            stream)
+    if rc != L7M_OK:
+        raise L7Error(rc, "l7m_kafka_stream_frame_device failed")
 
 
 # --------------------------------------------------------------------------

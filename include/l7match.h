@@ -421,6 +421,110 @@ int l7m_http_wire_decode_device(const void* d_wire, size_t wire_bytes, const voi
 int64_t l7m_http_wire_encode(const uint8_t* arena, size_t arena_bytes, const uint64_t* rec_offsets, size_t n,
                              uint8_t* wire, size_t cap, uint64_t* head_offs /* n+1 */, int32_t* status);
 
+/* ---- connection byte streams (DESIGN.md "Stream framing") -----------------
+ * What a proxy or a capture holds is connections, not heads or records:
+ * connection c is wire[conn_offs[c], conn_offs[c+1]) (n_conns + 1 ascending
+ * offsets, the last <= wire_bytes).  Framing finds the requests inside each
+ * connection, sequentially within it and independently across connections,
+ * and writes the arrays the decoder (HTTP) or the evaluator (Kafka) takes.
+ *
+ * conn_status[c] is one of the codes below; conn_consumed[c] is the number of
+ * the connection's bytes up to the end of its last complete request (head and
+ * whole body, or frame; after L7M_STREAM_TUNNEL the CONNECT head included).
+ * Carrying the unconsumed tail over to a later call is the caller's job.
+ *
+ * HTTP: every attempt to read a head at a position yields one slice that
+ * starts there, so the slices of a connection tile its bytes and
+ * head_offs[0 .. n_heads] (head_offs[n_heads] = conn_offs[n_conns]) is what
+ * l7m_http_wire_decode(_device) takes unchanged.  A refused or partial last
+ * head is a slice too: it decodes to the L7M_WIRE_E* code that ended the
+ * connection.  How to read conn_status for the LAST slice of a connection:
+ *   EAMBIGUOUS / EBADTE / EBADLENGTH  the head is complete and is evaluated,
+ *       but a proxy would have answered 400 instead: discard its verdict;
+ *   EBADCHUNK / EPARTIAL_BODY  the head was complete and its verdict stands;
+ *   EBADHEAD / EPARTIAL_HEAD   the slice decodes to a negative wire status.
+ * Kafka: a frame is the 4-byte big-endian size and `size` bytes; a bad size
+ * or a cut frame ends the connection and emits nothing (the reference's
+ * handler is never called for it).  A well-framed request that the evaluator
+ * answers with L7M_VERDICT_PARSE_ERROR also closes its connection in the
+ * reference; the framer does not look inside frames: rec_conn lets a caller
+ * drop a connection's records after its first such verdict. */
+#define L7M_STREAM_OK 0              /* the connection ends where a request ends (or is empty) */
+#define L7M_STREAM_TUNNEL 1          /* HTTP: a CONNECT head; the rest is opaque               */
+#define L7M_STREAM_EBADHEAD (-1)     /* HTTP: the decoder refuses the head (status < -1)       */
+#define L7M_STREAM_EPARTIAL_HEAD (-2)  /* HTTP: the bytes end inside a head                    */
+#define L7M_STREAM_EAMBIGUOUS (-3)   /* HTTP: transfer-encoding together with content-length   */
+#define L7M_STREAM_EBADTE (-4)       /* HTTP: transfer-encoding is not one line `chunked`      */
+#define L7M_STREAM_EBADLENGTH (-5)   /* HTTP: content-length is not one line of 1-18 digits    */
+#define L7M_STREAM_EBADCHUNK (-6)    /* HTTP: chunk size, extension, line end or trailer       */
+#define L7M_STREAM_EPARTIAL_BODY (-7)  /* HTTP: the bytes end inside a body                    */
+#define L7M_STREAM_EPARTIAL_FRAME (-8) /* Kafka: the bytes end inside a size field or a frame  */
+#define L7M_STREAM_EBADSIZE (-9)     /* Kafka: size < 8 or size + 4 > 6553500                  */
+
+/* Heads that any n_conns connections in wire_bytes bytes can yield:
+ * wire_bytes / 16 + n_conns.  A slice that is followed by another one in its
+ * connection holds a complete head, and a complete head is at least 16 bytes
+ * (`G / HTTP/1.1 CRLF CRLF`); each connection adds at most one last slice. */
+size_t l7m_http_stream_heads_bound(size_t wire_bytes, size_t n_conns);
+/* Host framer (no device needed), and the definition the device framer
+ * reproduces byte for byte.  head_conn[i] is the connection of head i and
+ * head_meta[i] = conn_meta[head_conn[i]] (what lookupNewDest gives once per
+ * connection; head_meta NULL: not written; conn_meta NULL: zeros, ingress).
+ * conn_status, conn_consumed and *n_heads are always complete.  When
+ * *n_heads > cap_heads the per-head arrays are untouched and the call returns
+ * L7M_ENOMEM (cap_heads == 0 with NULL arrays is the sizing call); otherwise
+ * head_offs[0 .. *n_heads] and the first *n_heads entries of the others are
+ * written.  L7M_EINVAL for conn_offs that do not ascend or pass wire_bytes. */
+int l7m_http_stream_frame(const uint8_t* wire, size_t wire_bytes, const uint64_t* conn_offs /* n_conns + 1 */,
+                          size_t n_conns, const l7m_http_wire_meta* conn_meta /* NULL or n_conns */,
+                          uint64_t* head_offs /* cap_heads + 1 */, uint32_t* head_conn /* cap_heads */,
+                          l7m_http_wire_meta* head_meta /* NULL or cap_heads */, size_t cap_heads,
+                          int32_t* conn_status, uint64_t* conn_consumed, size_t* n_heads);
+/* The same on device buffers, enqueued on hip_stream (NULL = default stream)
+ * without synchronising: a count pass, a scan and an emit pass, one
+ * connection per lane.  *d_n_heads (u64) stays on the device; the decoder and
+ * the evaluator take n as a host argument, so the caller reads those 8 bytes
+ * back once between framing and decoding.  Offsets that do not ascend give
+ * unspecified output, without reading outside d_wire. */
+int l7m_http_stream_frame_device(const void* d_wire, size_t wire_bytes, const void* d_conn_offs, size_t n_conns,
+                                 const void* d_conn_meta, void* d_head_offs, void* d_head_conn, void* d_head_meta,
+                                 size_t cap_heads, void* d_conn_status, void* d_conn_consumed,
+                                 void* d_n_heads /* u64 */, void* hip_stream);
+
+/* Records that wire_bytes bytes can yield: wire_bytes / 12 (the smallest frame
+ * is the size field and 8 bytes).  Arena bytes that are enough for them:
+ * wire_bytes + wire_bytes / 4.  Derivation: a frame of F >= 12 bytes takes
+ * round_up(F, 4) <= F + 3 <= F + F / 4 arena bytes, and F + F / 4 (integer
+ * division) is superadditive, so the sum over the frames is at most
+ * g(wire_bytes).  The bound is met by frames of 13 bytes (size 9): 16 arena
+ * bytes each.  A device arena additionally needs the evaluator's readable
+ * slack: allocate round_up(bound, 16). */
+size_t l7m_kafka_stream_records_bound(size_t wire_bytes);
+size_t l7m_kafka_stream_arena_bound(size_t wire_bytes);
+/* Host framer.  Each frame is copied to a 4-byte-aligned slot of `arena`
+ * (the evaluator wants dword-aligned records, a socket does not give them)
+ * with zero pad bytes: arena + rec_offsets is what l7m_eval(_ids) takes.
+ * rec_conn[i] is the connection of record i and src_identities[i] =
+ * conn_identity[rec_conn[i]] (src_identities NULL: not written;
+ * conn_identity NULL: zeros).  conn_status, conn_consumed, *n_recs and
+ * *arena_bytes are always complete.  When *n_recs > cap_recs or
+ * *arena_bytes > cap_bytes the per-record arrays and the arena are untouched
+ * and the call returns L7M_ENOMEM (zero capacities with NULL arrays are the
+ * sizing call).  L7M_EINVAL as above. */
+int l7m_kafka_stream_frame(const uint8_t* wire, size_t wire_bytes, const uint64_t* conn_offs, size_t n_conns,
+                           const uint32_t* conn_identity /* NULL or n_conns */, uint8_t* arena, size_t cap_bytes,
+                           uint64_t* rec_offsets, uint32_t* rec_conn, uint32_t* src_identities /* NULL or cap_recs */,
+                           size_t cap_recs, int32_t* conn_status, uint64_t* conn_consumed, size_t* n_recs,
+                           size_t* arena_bytes);
+/* The same on device buffers (d_arena 16-byte aligned), enqueued without
+ * synchronising: count pass, two scans, emit pass and a copy kernel balanced
+ * over the arena.  *d_n_recs and *d_arena_bytes are u64. */
+int l7m_kafka_stream_frame_device(const void* d_wire, size_t wire_bytes, const void* d_conn_offs, size_t n_conns,
+                                  const void* d_conn_identity, void* d_arena, size_t cap_bytes, void* d_rec_offsets,
+                                  void* d_rec_conn, void* d_src_identities, size_t cap_recs, void* d_conn_status,
+                                  void* d_conn_consumed, void* d_n_recs /* u64 */, void* d_arena_bytes /* u64 */,
+                                  void* hip_stream);
+
 /* ---- evaluation flags ------------------------------------------------------
  * 0 for normal use. The DIAG flags select profiling ablations of the HTTP
  * kernel whose verdicts are NOT valid (used by bench.py --diag).  HTTP
