@@ -305,8 +305,19 @@ struct LdsChain {
     return src.word_u(p);
   }
   // continue the walk over bytes [k, len) of the field at pos
-  template <class Src>
+  // kTailWord (the lean kernel, on the LDS stage only): the field's last 1-3
+  // bytes come from ONE word read, requested here with the first block's
+  // words, so the tail's steps start with no stage read of their own (a byte
+  // read per step, each behind its own wait, otherwise).  The word may cover
+  // up to 3 bytes past the field (the next field, pad, the next record or the
+  // stage's 16 spare bytes): the steps on them are masked by the length.
+  // Records read from HBM keep the byte reads: nothing at or past pos + len
+  // is read there.
+  template <bool kTailWord = false, class Src>
   __device__ __forceinline__ void run(const Src& src, uint32_t pos, uint32_t len, uint32_t k) {
+    constexpr bool kTw = kTailWord && Src::kLds;
+    uint32_t tw = 0;
+    if constexpr (kTw) tw = word_at(src, pos + len - ((len - k) & 3u));
     for (; k + 8 <= len; k += 8) {
       const uint32_t w0 = word_at(src, pos + k), w1 = word_at(src, pos + k + 4);
       if (__any((e >> kLdsRowShift) < lim)) {  // some lane may still leave the multi-pattern region
@@ -340,10 +351,22 @@ struct LdsChain {
       pw = w0;
       k += 4;
     }
-    for (; k < len; ++k) {
-      const uint32_t b = src.byte(pos + k);
-      L7M_OSTEP(b, "BYTE_0", pw, "BYTE_3", true)
-      pw = b << 24;
+    if constexpr (kTw) {
+      const uint32_t r = len - k;  // 0-3 bytes left, bytes 0 .. r - 1 of tw
+      if (r) {
+        L7M_OSTEP(tw, "BYTE_0", pw, "BYTE_3", true)
+        if (r > 1) {
+          L7M_OSTEP(tw, "BYTE_1", tw, "BYTE_0", true)
+          if (r > 2) L7M_OSTEP(tw, "BYTE_2", tw, "BYTE_1", true)
+        }
+        pw = tw << (32u - 8u * r);  // byte 3: the last byte consumed
+      }
+    } else {
+      for (; k < len; ++k) {
+        const uint32_t b = src.byte(pos + k);
+        L7M_OSTEP(b, "BYTE_0", pw, "BYTE_3", true)
+        pw = b << 24;
+      }
     }
   }
   // The end code of a table whose entries carry it (lds_es == kLdsEsInEntry),
@@ -1063,9 +1086,33 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const H& h, const Src
   const uint32_t mlen = w3 & 0xffffu, plen = w3 >> 16, alen = w4 & 0xffffu;
   uint64_t need = L7M_HTTP_REC_FIXED + 4ull * nhdr + mlen + plen + alen;
   if (need > w0 || ((static_cast<uint64_t>(w0) + 3) & ~3ull) > limit) return L7M_VERDICT_PARSE_ERROR;
-  for (uint32_t j = 0; j < nhdr; ++j) {
-    const uint32_t e = src.word(5 + j);
-    need += (e & 0xffffu) + (e >> 16);
+  // kScan (the lean kernel, on the LDS stage): this pass over the directory,
+  // whose reads are independent, also finds the first header whose name
+  // length a rule references -- index, entry word and the bytes in front of
+  // it (32 bits: it may lie past byte 65,535 of a large record) -- so header
+  // job 3 starts from registers and not from a second, serial pass whose
+  // every read waits for the one before (the tile pays for its longest
+  // directory).  Later header jobs continue from the cursor as before.
+  constexpr bool kScan = kLean && Src::kLds;
+  uint32_t cand_j = nhdr, cand_e = 0, cand_off = 0;
+  if constexpr (kScan) {
+    uint32_t run = 0;
+    for (uint32_t j = 0; j < nhdr; ++j) {
+      const uint32_t e = src.word(5 + j);
+      const uint32_t nl = e & 0xffffu, lb = nl < 63 ? nl : 63;
+      const bool ref = ((lb < 32 ? h.name_len_lo >> lb : h.name_len_hi >> (lb - 32)) & 1u) != 0;
+      const bool first = ref && cand_j == nhdr;
+      cand_j = first ? j : cand_j;
+      cand_e = first ? e : cand_e;
+      cand_off = first ? run : cand_off;
+      run += nl + (e >> 16);
+    }
+    need += run;  // (<= 255 x 131,070)
+  } else {
+    for (uint32_t j = 0; j < nhdr; ++j) {
+      const uint32_t e = src.word(5 + j);
+      need += (e & 0xffffu) + (e >> 16);
+    }
   }
   if (need != w0) return L7M_VERDICT_PARSE_ERROR;
 
@@ -1141,11 +1188,17 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const H& h, const Src
       if constexpr (!kLean)  // (lean: without a name table the masks are empty, http_program_lean)
         if (!h.has_name_dfa) break;
       uint32_t e = 0;
-      for (; hj < nhdr; ++hj) {
-        e = src.word(5 + hj);
-        const uint32_t nl = e & 0xffffu, lb = nl < 63 ? nl : 63;
-        if ((lb < 32 ? h.name_len_lo >> lb : h.name_len_hi >> (lb - 32)) & 1u) break;
-        hp += nl + (e >> 16);  // no rule references a header name of this length
+      if (kScan && job == 3) {  // the validation pass found the first candidate
+        e = cand_e;
+        hj = cand_j;
+        hp += cand_off;
+      } else {
+        for (; hj < nhdr; ++hj) {
+          e = src.word(5 + hj);
+          const uint32_t nl = e & 0xffffu, lb = nl < 63 ? nl : 63;
+          if ((lb < 32 ? h.name_len_lo >> lb : h.name_len_hi >> (lb - 32)) & 1u) break;
+          hp += nl + (e >> 16);  // no rule references a header name of this length
+        }
       }
       if (!__any(hj < nhdr)) break;
       if (hj < nhdr) {
@@ -1176,7 +1229,7 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const H& h, const Src
           LdsChain ch;
           ch.init(dd);
           if (!dd.start_base) ch.e = 0;  // dead from the start: the dead row (walk_lds skips the walk: the same code, 0)
-          ch.run(src, p, len, 0);
+          ch.template run<true>(src, p, len, 0);  // (field tails from one word on the LDS stage)
           const uint32_t code = ch.code_in_entry(c.img, dd.lds_latch, dd.start_latch);
           HPROF(3);
           codes.set(d, code);
