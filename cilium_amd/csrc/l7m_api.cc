@@ -32,6 +32,11 @@ void set_err(char* err, size_t errlen, const std::string& m) {
   err[k] = '\0';
 }
 
+// The ABI status of a device pipeline's launcher (l7m_device.h launch_*).
+static int status_of(hipError_t e) {
+  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+}
+
 // Older callers may pass a shorter l7m_opts (struct_size): copy what they set.
 l7m_opts norm_opts(const l7m_opts* o) {
   l7m_opts r{};
@@ -667,7 +672,7 @@ int l7m_http_wire_decode_device(const void* d_wire, size_t wire_bytes, const voi
       static_cast<const l7m_http_wire_meta*>(d_meta), static_cast<uint8_t*>(d_arena), cap,
       static_cast<uint64_t*>(d_rec_offsets), static_cast<int32_t*>(d_status), static_cast<uint64_t*>(d_arena_bytes),
       static_cast<hipStream_t>(hip_stream));
-  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+  return status_of(e);
 }
 
 int l7m_http_stream_frame_device(const void* d_wire, size_t wire_bytes, const void* d_conn_offs, size_t n_conns,
@@ -685,7 +690,7 @@ int l7m_http_stream_frame_device(const void* d_wire, size_t wire_bytes, const vo
       static_cast<uint32_t*>(d_head_conn), static_cast<l7m_http_wire_meta*>(d_head_meta), cap_heads,
       static_cast<int32_t*>(d_conn_status), static_cast<uint64_t*>(d_conn_consumed),
       static_cast<uint64_t*>(d_n_heads), static_cast<hipStream_t>(hip_stream));
-  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+  return status_of(e);
 }
 
 int l7m_kafka_stream_frame_device(const void* d_wire, size_t wire_bytes, const void* d_conn_offs, size_t n_conns,
@@ -707,7 +712,7 @@ int l7m_kafka_stream_frame_device(const void* d_wire, size_t wire_bytes, const v
       static_cast<uint32_t*>(d_src_identities), cap_recs, static_cast<int32_t*>(d_conn_status),
       static_cast<uint64_t*>(d_conn_consumed), static_cast<uint64_t*>(d_n_recs),
       static_cast<uint64_t*>(d_arena_bytes), static_cast<hipStream_t>(hip_stream));
-  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+  return status_of(e);
 }
 
 int l7m_http_access_log_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
@@ -740,7 +745,7 @@ int l7m_http_access_log_device(const void* d_arena, size_t arena_bytes, const vo
       static_cast<const int32_t*>(d_verdicts), c, select ? select : (L7M_LOG_FORWARDED | L7M_LOG_DENIED),
       static_cast<uint8_t*>(d_out), cap, static_cast<uint64_t*>(d_entry_offs), static_cast<uint64_t*>(d_total),
       static_cast<hipStream_t>(hip_stream));
-  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+  return status_of(e);
 }
 
 int l7m_kafka_deny_responses_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
@@ -755,7 +760,7 @@ int l7m_kafka_deny_responses_device(const void* d_arena, size_t arena_bytes, con
       false, static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets), n,
       static_cast<const int32_t*>(d_verdicts), 0, static_cast<uint8_t*>(d_out), cap,
       static_cast<uint64_t*>(d_resp_offs), static_cast<uint64_t*>(d_total), static_cast<hipStream_t>(hip_stream));
-  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+  return status_of(e);
 }
 
 int l7m_kafka_access_log_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
@@ -771,7 +776,7 @@ int l7m_kafka_access_log_device(const void* d_arena, size_t arena_bytes, const v
       true, static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets), n,
       static_cast<const int32_t*>(d_verdicts), select, static_cast<uint8_t*>(d_out), cap,
       static_cast<uint64_t*>(d_first), static_cast<uint64_t*>(d_total), static_cast<hipStream_t>(hip_stream));
-  return e == hipSuccess ? L7M_OK : e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+  return status_of(e);
 }
 
 int l7m_proxy_stats_update_device(l7m_proxy_stats_table* t, uint32_t proto, const void* d_arena, size_t arena_bytes,
@@ -787,7 +792,7 @@ int l7m_proxy_stats_update_device(l7m_proxy_stats_table* t, uint32_t proto, cons
       static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets),
       static_cast<const int32_t*>(d_verdicts), n, (ingress ? 65536u : 0u) | port, counters.data(),
       static_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return e == hipErrorOutOfMemory ? L7M_ENOMEM : L7M_EDEVICE;
+  if (e != hipSuccess) return status_of(e);
   proxy_stats_merge_http(t, counters.data());
   return L7M_OK;
 }

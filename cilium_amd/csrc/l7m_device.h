@@ -114,7 +114,8 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
                        const DoneSignal* done = nullptr);
 
 // HTTP/1.x request heads -> request arena (l7m_http_wire.hip): measure pass,
-// scan and emit pass enqueued on `stream`; scratch from scratch_alloc_async.
+// scan and emit pass enqueued on `stream` by l7m_tile_scan.h's tile_pipeline,
+// as in the four pipeline launchers after it; scratch from scratch_alloc_async.
 // *total (u64) receives the arena bytes; nothing of `arena` is written when
 // that exceeds cap.
 hipError_t launch_http_wire(const uint8_t* wire, uint64_t wire_bytes, const uint64_t* head_offs, uint64_t n,

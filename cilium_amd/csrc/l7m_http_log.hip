@@ -3,12 +3,13 @@
 // l7m_proxy_stats_update_device; the entry and the record validation in
 // l7m_http_log.h, shared with the host functions of l7m_side.cc).
 //
-// Access log: the wire decoder's shape (l7m_http_wire.hip).  A workgroup owns
-// a tile of kLogTile consecutive requests, one per lane.
+// Access log: a measure / scan / emit pipeline on l7m_tile_scan.h's scaffold.
+// A workgroup owns a tile of kTileThreads consecutive requests, one per lane.
 //   measure: entry size per request from the record's fixed part and
 //            directory, read from global memory; the tile's size sum
-//   scan:    exclusive sum of the tile sums (l7m_tile_scan.h), the total
-//   emit:    entry offsets and, when the total fits, the entries.  The
+//   scan:    exclusive sum of the tile sums, the total
+//   emit:    entry offsets (entry_offs[0, n], entry n the total) and, when
+//            the total fits, the entries.  The
 //            records of the lanes that have an entry are staged into LDS with
 //            aligned 16-byte loads, a window of kLogStage arena bytes at a
 //            time starting at the lowest record not yet served; a lane whose
@@ -37,17 +38,10 @@
 namespace l7m {
 namespace {
 
-constexpr uint32_t kLogTile = kTileThreads;   // requests per workgroup = threads per workgroup
 constexpr uint32_t kLogStage = 64u * 1024u;   // staged arena bytes per window (256 per request)
 
-// The arena in global memory (16-byte aligned; record offsets are 4-aligned).
-struct LogGlobalSrc {
-  const uint8_t* p;
-  __device__ uint8_t at(uint64_t i) const { return p[i]; }
-  __device__ uint32_t word(uint64_t i) const { return *reinterpret_cast<const uint32_t*>(p + i); }
-};
-
-// Arena bytes [base, base + staged) in LDS, base a multiple of 16.
+// The arena in global memory (16-byte aligned; record offsets are 4-aligned)
+// is a ByteSrc.  Arena bytes [base, base + staged) in LDS, base a multiple of 16.
 struct LogLdsSrc {
   const uint8_t* lds;
   uint64_t base;
@@ -88,23 +82,22 @@ struct LogOutSink {
   }
 };
 
-__global__ __launch_bounds__(kLogTile) void http_log_measure(const uint8_t* arena, uint64_t arena_bytes,
-                                                             const uint64_t* offs, uint64_t n,
-                                                             const int32_t* verdicts, const LogConstsFixed c,
-                                                             uint32_t select, uint64_t* sizes /* = entry_offs */,
-                                                             uint64_t* tile_sums) {
-  __shared__ uint64_t tmp[kLogTile];
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kLogTile + threadIdx.x;
+__global__ __launch_bounds__(kTileThreads) void http_log_measure(const uint8_t* arena, uint64_t arena_bytes,
+                                                                 const uint64_t* offs, uint64_t n,
+                                                                 const int32_t* verdicts, const LogConstsFixed c,
+                                                                 uint32_t select, uint64_t* sizes /* = entry_offs */,
+                                                                 uint64_t* tile_sums) {
+  __shared__ uint64_t tmp[kTileThreads];
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
   uint64_t size = 0;
   if (i < n) {
     const int32_t vd = verdicts[i];
-    const LogGlobalSrc src{arena};
+    const ByteSrc src{arena};
     LogView v;
     if (log_wanted(vd, select) && log_view(src, arena_bytes, offs[i], v)) size = log_measure(src, v, vd, c);
     sizes[i] = size;
   }
-  const uint64_t incl = block_inclusive(size, tmp);
-  if (threadIdx.x == kLogTile - 1) tile_sums[blockIdx.x] = incl;
+  tile_sum_out(size, tmp, tile_sums);
 }
 
 // Window control words in LDS.
@@ -114,18 +107,19 @@ struct LogCtl {
   uint32_t pad;
 };
 constexpr unsigned long long kLogNone = ~0ull;
+constexpr uint32_t kLogLds = kLogStage + kTileThreads * sizeof(uint64_t) + sizeof(LogCtl);  // stage, tmp, ctl
 
-__global__ __launch_bounds__(kLogTile) void http_log_emit(const uint8_t* arena, uint64_t arena_bytes,
-                                                          const uint64_t* offs, uint64_t n, const int32_t* verdicts,
-                                                          const LogConstsFixed c, uint8_t* out, uint64_t cap,
-                                                          uint64_t* entry_offs, const uint64_t* tile_base,
-                                                          const uint64_t* total) {
+__global__ __launch_bounds__(kTileThreads) void http_log_emit(const uint8_t* arena, uint64_t arena_bytes,
+                                                              const uint64_t* offs, uint64_t n,
+                                                              const int32_t* verdicts, const LogConstsFixed c,
+                                                              uint8_t* out, uint64_t cap, uint64_t* entry_offs,
+                                                              const uint64_t* tile_base, const uint64_t* total) {
   extern __shared__ __attribute__((aligned(16))) uint8_t log_smem[];
   uint64_t* tmp = reinterpret_cast<uint64_t*>(log_smem + kLogStage);
-  LogCtl* ctl = reinterpret_cast<LogCtl*>(tmp + kLogTile);
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kLogTile + threadIdx.x;
+  LogCtl* ctl = reinterpret_cast<LogCtl*>(tmp + kTileThreads);
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
   const uint64_t size = i < n ? entry_offs[i] : 0;  // the measure pass left the sizes here
-  const uint64_t eoff = tile_base[blockIdx.x] + block_inclusive(size, tmp) - size;
+  const uint64_t eoff = tile_exclusive(size, tmp, tile_base);
   const uint64_t all = *total;
   if (i < n) entry_offs[i] = eoff;
   if (i + 1 == n) entry_offs[n] = all;
@@ -136,7 +130,7 @@ __global__ __launch_bounds__(kLogTile) void http_log_emit(const uint8_t* arena, 
   int32_t vd = 0;
   if (todo) {
     lo = offs[i];
-    hi = lo + LogGlobalSrc{arena}.word(lo);
+    hi = lo + ByteSrc{arena}.word(lo);
     vd = verdicts[i];
   }
   auto emit = [&](const auto& src) {
@@ -162,14 +156,14 @@ __global__ __launch_bounds__(kLogTile) void http_log_emit(const uint8_t* arena, 
     __syncthreads();
     // base + end <= arena_bytes, and the arena is readable to the next multiple of 16
     const uint32_t units = (ctl->end + 15u) >> 4;
-    for (uint32_t u = threadIdx.x; u < units; u += kLogTile)
+    for (uint32_t u = threadIdx.x; u < units; u += kTileThreads)
       *reinterpret_cast<uint4*>(log_smem + 16u * u) = *reinterpret_cast<const uint4*>(arena + base + 16ull * u);
     __syncthreads();
     if (staged) {
       emit(LogLdsSrc{log_smem, base});
       todo = false;
     } else if (todo && lo == first) {  // larger than the window
-      emit(LogGlobalSrc{arena});
+      emit(ByteSrc{arena});
       todo = false;
     }
     __syncthreads();
@@ -177,32 +171,32 @@ __global__ __launch_bounds__(kLogTile) void http_log_emit(const uint8_t* arena, 
 }
 
 // ---- proxy statistics -------------------------------------------------------
-constexpr uint32_t kStatsSpan = 8;                         // tiles per workgroup
-constexpr uint32_t kStatsSlots = 2 * kStatsSpan * kLogTile;  // LDS hash slots: at most half of them fill
+constexpr uint32_t kStatsSpan = 8;                               // tiles per workgroup
+constexpr uint32_t kStatsSlots = 2 * kStatsSpan * kTileThreads;  // LDS hash slots: at most half of them fill
 constexpr uint32_t kStatsEmpty = 0xffffffffu;
 static_assert(kStatsSlots == 1u << 12, "http_stats_count hashes a key to 12 bits");
 
-__global__ __launch_bounds__(kLogTile) void http_stats_count(const uint8_t* arena, uint64_t arena_bytes,
-                                                             const uint64_t* offs, const int32_t* verdicts,
-                                                             uint64_t n, uint32_t caller_row,
-                                                             unsigned long long* counters /* kStatsCounters */) {
+__global__ __launch_bounds__(kTileThreads) void http_stats_count(const uint8_t* arena, uint64_t arena_bytes,
+                                                                 const uint64_t* offs, const int32_t* verdicts,
+                                                                 uint64_t n, uint32_t caller_row,
+                                                                 unsigned long long* counters /* kStatsCounters */) {
   __shared__ uint32_t keys[kStatsSlots];
   __shared__ uint32_t counts[kStatsSlots];
-  for (uint32_t s = threadIdx.x; s < kStatsSlots; s += kLogTile) {
+  for (uint32_t s = threadIdx.x; s < kStatsSlots; s += kTileThreads) {
     keys[s] = kStatsEmpty;
     counts[s] = 0;
   }
   __syncthreads();
-  const uint64_t first = static_cast<uint64_t>(blockIdx.x) * kStatsSpan * kLogTile;
+  const uint64_t first = static_cast<uint64_t>(blockIdx.x) * kStatsSpan * kTileThreads;
   const uint32_t lane = __lane_id();
   for (uint32_t t = 0; t < kStatsSpan; ++t) {  // uniform
-    const uint64_t i = first + static_cast<uint64_t>(t) * kLogTile + threadIdx.x;
+    const uint64_t i = first + static_cast<uint64_t>(t) * kTileThreads + threadIdx.x;
     const bool active = i < n;
     uint32_t key = 0;
     if (active) {
       LogView v;
       uint32_t row = caller_row;  // a record that does not validate: the caller's port and direction
-      if (log_view(LogGlobalSrc{arena}, arena_bytes, offs[i], v))
+      if (log_view(ByteSrc{arena}, arena_bytes, offs[i], v))
         row = ((v.flags & L7M_HTTP_F_INGRESS) ? 65536u : 0u) | v.dport;
       key = row * kStatsClasses + flow_verdict(verdicts[i]);
     }
@@ -225,7 +219,7 @@ __global__ __launch_bounds__(kLogTile) void http_stats_count(const uint8_t* aren
     }
   }
   __syncthreads();
-  for (uint32_t s = threadIdx.x; s < kStatsSlots; s += kLogTile)
+  for (uint32_t s = threadIdx.x; s < kStatsSlots; s += kTileThreads)
     if (counts[s]) atomicAdd(counters + keys[s], static_cast<unsigned long long>(counts[s]));
 }
 
@@ -239,37 +233,32 @@ hipError_t launch_http_log(const uint8_t* arena, uint64_t arena_bytes, const uin
     if (e == hipSuccess && entry_offs) e = hipMemsetAsync(entry_offs, 0, sizeof(uint64_t), stream);
     return e;
   }
-  const uint64_t tiles = (n + kLogTile - 1) / kLogTile;
-  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
-  const uint32_t lds = kLogStage + kLogTile * sizeof(uint64_t) + sizeof(LogCtl);
-  hipError_t e = set_lds_attr_once(reinterpret_cast<const void*>(&http_log_emit), lds);
+  const hipError_t e = set_lds_attr_once(reinterpret_cast<const void*>(&http_log_emit), kLogLds);
   if (e != hipSuccess) return e;
-  void* scratch = nullptr;
-  e = scratch_alloc_async(&scratch, tiles * sizeof(uint64_t), stream);
-  if (e != hipSuccess) return e;
-  uint64_t* tile_sums = static_cast<uint64_t*>(scratch);
-  http_log_measure<<<dim3(static_cast<uint32_t>(tiles)), dim3(kLogTile), 0, stream>>>(
-      arena, arena_bytes, offs, n, verdicts, c, select, entry_offs, tile_sums);
-  http_wire_scan_tiles<<<dim3(1), dim3(kScanThreads), 0, stream>>>(tile_sums, tiles, total);
-  http_log_emit<<<dim3(static_cast<uint32_t>(tiles)), dim3(kLogTile), lds, stream>>>(
-      arena, arena_bytes, offs, n, verdicts, c, out, cap, entry_offs, tile_sums, total);
-  e = hipGetLastError();
-  const hipError_t f = hipFreeAsync(scratch, stream);
-  return e != hipSuccess ? e : f;
+  return tile_pipeline(
+      n, {total}, 0, stream,
+      [&](uint32_t tiles, uint64_t* tile_sums, void*) {
+        http_log_measure<<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(arena, arena_bytes, offs, n, verdicts, c,
+                                                                         select, entry_offs, tile_sums);
+      },
+      [&](uint32_t tiles, const uint64_t* tile_base, void*) {
+        http_log_emit<<<dim3(tiles), dim3(kTileThreads), kLogLds, stream>>>(
+            arena, arena_bytes, offs, n, verdicts, c, out, cap, entry_offs, tile_base, total);
+      });
 }
 
 hipError_t launch_http_stats(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs,
                              const int32_t* verdicts, uint64_t n, uint32_t caller_row, uint64_t* host_counters,
                              hipStream_t stream) {
-  const uint64_t groups = (n + kStatsSpan * kLogTile - 1) / (kStatsSpan * kLogTile);
+  const uint64_t groups = (n + kStatsSpan * kTileThreads - 1) / (kStatsSpan * kTileThreads);
   if (groups > 0x7fffffffull) return hipErrorInvalidValue;
   const size_t bytes = static_cast<size_t>(kStatsCounters) * sizeof(uint64_t);
-  void* scratch = nullptr;
+  void* scratch = nullptr;  // one kernel, no sizes or scan: not a tile_pipeline, so the scratch is handled here
   hipError_t e = scratch_alloc_async(&scratch, bytes, stream);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(scratch, 0, bytes, stream);
   if (e == hipSuccess && groups) {
-    http_stats_count<<<dim3(static_cast<uint32_t>(groups)), dim3(kLogTile), 0, stream>>>(
+    http_stats_count<<<dim3(static_cast<uint32_t>(groups)), dim3(kTileThreads), 0, stream>>>(
         arena, arena_bytes, offs, verdicts, n, caller_row, static_cast<unsigned long long*>(scratch));
     e = hipGetLastError();
   }

@@ -3,14 +3,14 @@
 // shared with the host decoder).
 //
 // Two passes over the wire bytes with a scan between them.  A workgroup owns
-// a tile of kWireTile consecutive heads, whose bytes are one contiguous range
-// of the wire.  It stages as many of them as fit kWireStage bytes of LDS with
+// a tile of kTileThreads consecutive heads, whose bytes are one contiguous
+// range of the wire.  It stages as many of them as fit kWireStage bytes of LDS with
 // aligned 16-byte loads (a chunk; an ordinary tile is one chunk) and parses
 // them one head per lane from LDS.  A head that does not fit the stage on its
 // own is walked from global memory by its lane.
 //   measure: status and padded record size per head, the tile's size sum
-//   scan:    exclusive sum of the tile sums (one workgroup), the total
-//   emit:    record offsets (tile base + sum inside the tile) and, when the
+//   scan:    exclusive sum of the tile sums, the total
+//   emit:    record offsets (rec_offsets[0, n); no entry n) and, when the
 //            total fits the arena, the records, one aligned dword per store
 //
 // Compiled as part of l7m_kernels.hip's translation unit (included at its
@@ -25,22 +25,8 @@
 namespace l7m {
 namespace {
 
-constexpr uint32_t kWireTile = kTileThreads;   // heads per workgroup = threads per workgroup (l7m_tile_scan.h)
 constexpr uint32_t kWireStage = 64u * 1024u;   // staged wire bytes per chunk (256 per head)
-
-// A staged head, read a byte at a time.  (Keeping an aligned 8-byte window of
-// the stage in registers, one ds_read_b64 per eight bytes, measured slower:
-// 11.9 ms against 8.7 ms on 8.2 M heads of config 2.  The parse is bound by
-// its per-byte branches, not by the LDS loads.)
-struct WireLdsSrc {
-  const uint8_t* p;
-  __device__ uint8_t at(uint64_t i) const { return p[i]; }
-};
-
-struct WireGlobalSrc {
-  const uint8_t* p;
-  __device__ uint8_t at(uint64_t i) const { return p[i]; }
-};
+constexpr uint32_t kWireLds = kWireStage + kTileThreads * sizeof(uint64_t) + 16;  // stage, tile_lo, s_end
 
 // Record bytes in order -> aligned dword stores (records are 4-byte aligned
 // and a multiple of four bytes long).
@@ -56,23 +42,6 @@ struct DwordSink {
   }
 };
 
-// The tile's head bounds, clamped to the wire so that no offset array can
-// lead a load outside it: head t of the tile is wire[lo, hi).
-struct HeadRange {
-  uint64_t lo, hi;
-};
-
-__device__ __forceinline__ HeadRange head_range(const uint64_t* head_offs, uint64_t i, uint64_t n, uint64_t wire_bytes) {
-  HeadRange r{0, 0};
-  if (i < n) {
-    const uint64_t a = head_offs[i], b = head_offs[i + 1];
-    r.lo = a < wire_bytes ? a : wire_bytes;
-    r.hi = b < wire_bytes ? b : wire_bytes;
-    if (r.hi < r.lo) r.hi = r.lo;
-  }
-  return r;
-}
-
 // Stage wire addresses [gbase, gend) (gbase 16-byte aligned) into lds[0, ...):
 // aligned 16-byte loads for the units inside the wire buffer, guarded bytes
 // for a unit that straddles one of its ends.
@@ -80,7 +49,7 @@ __device__ __forceinline__ void stage_chunk(uint8_t* lds, const uint8_t* wire, u
                                             uint64_t gend) {
   const uint64_t w0 = reinterpret_cast<uint64_t>(wire), w1 = w0 + wire_bytes;
   const uint32_t units = static_cast<uint32_t>((gend - gbase + 15) >> 4);
-  for (uint32_t u = threadIdx.x; u < units; u += kWireTile) {
+  for (uint32_t u = threadIdx.x; u < units; u += kTileThreads) {
     const uint64_t g = gbase + 16ull * u;
     uint4 v;
     if (g >= w0 && g + 16 <= w1) {
@@ -97,10 +66,15 @@ __device__ __forceinline__ void stage_chunk(uint8_t* lds, const uint8_t* wire, u
 }
 
 // Walks the tile chunk by chunk: f(src, len) runs once per head, on its lane,
-// with a WireLdsSrc for a staged head and a WireGlobalSrc for one larger than the stage.
+// with a ByteSrc into LDS for a staged head and into the wire for one larger
+// than the stage.  The head of lane t is wire[r.lo, r.hi) (clamped_range).
+// A staged head is read a byte at a time.  (Keeping an aligned 8-byte window
+// of the stage in registers, one ds_read_b64 per eight bytes, measured slower:
+// 11.9 ms against 8.7 ms on 8.2 M heads of config 2.  The parse is bound by
+// its per-byte branches, not by the LDS loads.)
 template <class F>
-__device__ __forceinline__ void for_each_head(uint8_t* lds, const uint8_t* wire, uint64_t wire_bytes, HeadRange r,
-                                              uint32_t cnt, const uint64_t* tile_lo /* LDS, kWireTile */,
+__device__ __forceinline__ void for_each_head(uint8_t* lds, const uint8_t* wire, uint64_t wire_bytes, ClampedRange r,
+                                              uint32_t cnt, const uint64_t* tile_lo /* LDS, kTileThreads */,
                                               uint64_t* s_end /* LDS, one word */, F&& f) {
   const uint64_t w0 = reinterpret_cast<uint64_t>(wire);
   uint32_t a = 0;
@@ -120,58 +94,59 @@ __device__ __forceinline__ void for_each_head(uint8_t* lds, const uint8_t* wire,
     __syncthreads();
     if (threadIdx.x >= a && threadIdx.x < a + k) {
       if (fits && w0 + r.hi <= gend)
-        f(WireLdsSrc{lds + (w0 + r.lo - gbase)}, r.hi - r.lo);
+        f(ByteSrc{lds + (w0 + r.lo - gbase)}, r.hi - r.lo);
       else
-        f(WireGlobalSrc{wire + r.lo}, r.hi - r.lo);
+        f(ByteSrc{wire + r.lo}, r.hi - r.lo);
     }
     __syncthreads();
     a += k;
   }
 }
 
-__global__ __launch_bounds__(kWireTile) void http_wire_measure(const uint8_t* wire, uint64_t wire_bytes,
-                                                               const uint64_t* head_offs, uint64_t n,
-                                                               uint64_t* sizes /* = rec_offsets */, int32_t* status,
-                                                               uint64_t* tile_sums) {
+__global__ __launch_bounds__(kTileThreads) void http_wire_measure(const uint8_t* wire, uint64_t wire_bytes,
+                                                                  const uint64_t* head_offs, uint64_t n,
+                                                                  uint64_t* sizes /* = rec_offsets */,
+                                                                  int32_t* status, uint64_t* tile_sums) {
   extern __shared__ __attribute__((aligned(16))) uint8_t wire_smem[];
   uint64_t* tile_lo = reinterpret_cast<uint64_t*>(wire_smem + kWireStage);
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWireTile + threadIdx.x;
-  const uint64_t left = n - static_cast<uint64_t>(blockIdx.x) * kWireTile;
-  const uint32_t cnt = left < kWireTile ? static_cast<uint32_t>(left) : kWireTile;
-  const HeadRange r = head_range(head_offs, i, n, wire_bytes);
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
+  const uint64_t left = n - static_cast<uint64_t>(blockIdx.x) * kTileThreads;
+  const uint32_t cnt = left < kTileThreads ? static_cast<uint32_t>(left) : kTileThreads;
+  const ClampedRange r = clamped_range(head_offs, i, n, wire_bytes);
   tile_lo[threadIdx.x] = r.lo;
   __syncthreads();
   uint64_t size = 0;
-  for_each_head(wire_smem, wire, wire_bytes, r, cnt, tile_lo, tile_lo + kWireTile, [&](const auto& src, uint64_t len) {
+  uint64_t* s_end = tile_lo + kTileThreads;
+  for_each_head(wire_smem, wire, wire_bytes, r, cnt, tile_lo, s_end, [&](const auto& src, uint64_t len) {
     WireInfo info;
     wire_scan(src, len, info);
     size = info.status < 0 ? L7M_HTTP_REC_FIXED : wire_padded(info.rec_len);
     status[i] = info.status;
     sizes[i] = size;
   });
-  const uint64_t incl = block_inclusive(size, tile_lo);
-  if (threadIdx.x == kWireTile - 1) tile_sums[blockIdx.x] = incl;
+  tile_sum_out(size, tile_lo, tile_sums);  // tile_lo is free after for_each_head's last barrier
 }
 
-__global__ __launch_bounds__(kWireTile) void http_wire_emit(const uint8_t* wire, uint64_t wire_bytes,
-                                                            const uint64_t* head_offs, uint64_t n,
-                                                            const l7m_http_wire_meta* meta, uint8_t* arena,
-                                                            uint64_t cap, uint64_t* rec_offsets,
-                                                            const uint64_t* tile_base, const uint64_t* total) {
+__global__ __launch_bounds__(kTileThreads) void http_wire_emit(const uint8_t* wire, uint64_t wire_bytes,
+                                                               const uint64_t* head_offs, uint64_t n,
+                                                               const l7m_http_wire_meta* meta, uint8_t* arena,
+                                                               uint64_t cap, uint64_t* rec_offsets,
+                                                               const uint64_t* tile_base, const uint64_t* total) {
   extern __shared__ __attribute__((aligned(16))) uint8_t wire_smem[];
   uint64_t* tile_lo = reinterpret_cast<uint64_t*>(wire_smem + kWireStage);
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWireTile + threadIdx.x;
-  const uint64_t left = n - static_cast<uint64_t>(blockIdx.x) * kWireTile;
-  const uint32_t cnt = left < kWireTile ? static_cast<uint32_t>(left) : kWireTile;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
+  const uint64_t left = n - static_cast<uint64_t>(blockIdx.x) * kTileThreads;
+  const uint32_t cnt = left < kTileThreads ? static_cast<uint32_t>(left) : kTileThreads;
   const uint64_t size = i < n ? rec_offsets[i] : 0;  // the measure pass left the sizes here
-  const uint64_t off = tile_base[blockIdx.x] + block_inclusive(size, tile_lo) - size;
+  const uint64_t off = tile_exclusive(size, tile_lo, tile_base);
   if (i < n) rec_offsets[i] = off;
   if (*total > cap) return;  // uniform: the arena stays untouched
-  __syncthreads();
-  const HeadRange r = head_range(head_offs, i, n, wire_bytes);
+  __syncthreads();  // tile_lo was the sum's tmp
+  const ClampedRange r = clamped_range(head_offs, i, n, wire_bytes);
   tile_lo[threadIdx.x] = r.lo;
   __syncthreads();
-  for_each_head(wire_smem, wire, wire_bytes, r, cnt, tile_lo, tile_lo + kWireTile, [&](const auto& src, uint64_t len) {
+  uint64_t* s_end = tile_lo + kTileThreads;
+  for_each_head(wire_smem, wire, wire_bytes, r, cnt, tile_lo, s_end, [&](const auto& src, uint64_t len) {
     WireInfo info;
     wire_scan(src, len, info);
     l7m_http_wire_meta m{0, 0, 0, 1, {0, 0, 0}};  // no metadata: zeros, ingress
@@ -188,24 +163,19 @@ hipError_t launch_http_wire(const uint8_t* wire, uint64_t wire_bytes, const uint
                             const l7m_http_wire_meta* meta, uint8_t* arena, uint64_t cap, uint64_t* rec_offsets,
                             int32_t* status, uint64_t* total, hipStream_t stream) {
   if (n == 0) return hipMemsetAsync(total, 0, sizeof(uint64_t), stream);
-  const uint64_t tiles = (n + kWireTile - 1) / kWireTile;
-  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
-  const uint32_t lds = kWireStage + kWireTile * sizeof(uint64_t) + 16;  // stage, tile_lo, s_end
-  hipError_t e = set_lds_attr_once(reinterpret_cast<const void*>(&http_wire_measure), lds);
-  if (e == hipSuccess) e = set_lds_attr_once(reinterpret_cast<const void*>(&http_wire_emit), lds);
+  hipError_t e = set_lds_attr_once(reinterpret_cast<const void*>(&http_wire_measure), kWireLds);
+  if (e == hipSuccess) e = set_lds_attr_once(reinterpret_cast<const void*>(&http_wire_emit), kWireLds);
   if (e != hipSuccess) return e;
-  void* scratch = nullptr;
-  e = scratch_alloc_async(&scratch, tiles * sizeof(uint64_t), stream);
-  if (e != hipSuccess) return e;
-  uint64_t* tile_sums = static_cast<uint64_t*>(scratch);
-  http_wire_measure<<<dim3(static_cast<uint32_t>(tiles)), dim3(kWireTile), lds, stream>>>(
-      wire, wire_bytes, head_offs, n, rec_offsets, status, tile_sums);
-  http_wire_scan_tiles<<<dim3(1), dim3(kScanThreads), 0, stream>>>(tile_sums, tiles, total);
-  http_wire_emit<<<dim3(static_cast<uint32_t>(tiles)), dim3(kWireTile), lds, stream>>>(
-      wire, wire_bytes, head_offs, n, meta, arena, cap, rec_offsets, tile_sums, total);
-  e = hipGetLastError();
-  const hipError_t f = hipFreeAsync(scratch, stream);
-  return e != hipSuccess ? e : f;
+  return tile_pipeline(
+      n, {total}, 0, stream,
+      [&](uint32_t tiles, uint64_t* tile_sums, void*) {
+        http_wire_measure<<<dim3(tiles), dim3(kTileThreads), kWireLds, stream>>>(wire, wire_bytes, head_offs, n,
+                                                                                 rec_offsets, status, tile_sums);
+      },
+      [&](uint32_t tiles, const uint64_t* tile_base, void*) {
+        http_wire_emit<<<dim3(tiles), dim3(kTileThreads), kWireLds, stream>>>(
+            wire, wire_bytes, head_offs, n, meta, arena, cap, rec_offsets, tile_base, total);
+      });
 }
 
 }  // namespace l7m

@@ -3,13 +3,13 @@
 // l7m_kafka_access_log_device; the request walk, the response and the record
 // fields in l7m_kafka_side.h, shared with the host functions of l7m_side.cc).
 //
-// The access-log encoder's shape (l7m_http_log.hip).  A workgroup owns a tile
-// of kLogTile consecutive requests, one per lane.
+// A measure / scan / emit pipeline on l7m_tile_scan.h's scaffold.  A workgroup
+// owns a tile of kTileThreads consecutive requests, one per lane.
 //   measure: the request is validated and walked; the response's size (or the
 //            number of its topics) per request, the tile's sum
-//   scan:    exclusive sum of the tile sums (l7m_tile_scan.h), the total
-//   emit:    offsets and, when the total fits, the output: the request is
-//            walked once more and the visitor writes as it goes
+//   scan:    exclusive sum of the tile sums, the total
+//   emit:    offsets [0, n] and, when the total fits, the output: the request
+//            is walked once more and the visitor writes as it goes
 // Both passes read the request from global memory byte by byte, each lane its
 // own: Kafka requests carry no alignment, and neighbouring lanes read
 // neighbouring requests, so the lines they share come from L2.  A request of
@@ -26,7 +26,7 @@
 // takes eight dependent shift-and-select steps.
 //
 // Compiled as part of l7m_kernels.hip's translation unit (included at its
-// end, after l7m_http_log.hip, whose LogOutSink and tile scan it uses).
+// end, after l7m_http_log.hip, whose LogOutSink it uses).
 #include <hip/hip_runtime.h>
 
 #include "l7m_device.h"
@@ -36,13 +36,9 @@
 namespace l7m {
 namespace {
 
-static_assert(kLogTile == 256, "a lane builds one entry of the CRC table");
+static_assert(kTileThreads == 256, "a lane builds one entry of the CRC table");
 
-// The arena in global memory; record offsets of any alignment.
-struct KsGlobalSrc {
-  const uint8_t* p;
-  __device__ uint8_t at(uint64_t i) const { return p[i]; }
-};
+// The arena is a ByteSrc read with at() only: record offsets have any alignment.
 
 struct KsCrcLds {
   const uint32_t* tab;  // LDS, 256 entries
@@ -90,20 +86,20 @@ struct KsLogEmit {
 // kLog: log records (sizes count records, `select` as kafka_log_wanted takes
 // it); otherwise deny responses (sizes count bytes, denied requests only).
 template <bool kLog>
-__global__ __launch_bounds__(kLogTile) void kafka_side_measure(const uint8_t* arena, uint64_t arena_bytes,
-                                                               const uint64_t* offs, uint64_t n,
-                                                               const int32_t* verdicts, uint32_t select,
-                                                               uint64_t* sizes /* = the output's offsets */,
-                                                               uint64_t* tile_sums) {
-  __shared__ uint64_t tmp[kLogTile];
+__global__ __launch_bounds__(kTileThreads) void kafka_side_measure(const uint8_t* arena, uint64_t arena_bytes,
+                                                                   const uint64_t* offs, uint64_t n,
+                                                                   const int32_t* verdicts, uint32_t select,
+                                                                   uint64_t* sizes /* = the output's offsets */,
+                                                                   uint64_t* tile_sums) {
+  __shared__ uint64_t tmp[kTileThreads];
   __shared__ uint32_t crc_tab[256];
   ks_crc_fill(crc_tab);
   __syncthreads();
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kLogTile + threadIdx.x;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
   uint64_t size = 0;
   if (i < n) {
     const int32_t vd = verdicts[i];
-    const KsGlobalSrc src{arena};
+    const ByteSrc src{arena};
     const uint64_t off = offs[i];
     uint64_t len = 0;
     if ((kLog ? kafka_log_wanted(vd, select) : vd == L7M_VERDICT_DENY) && kafka_rec(src, arena_bytes, off, &len)) {
@@ -118,28 +114,28 @@ __global__ __launch_bounds__(kLogTile) void kafka_side_measure(const uint8_t* ar
     }
     sizes[i] = size;
   }
-  const uint64_t incl = block_inclusive(size, tmp);
-  if (threadIdx.x == kLogTile - 1) tile_sums[blockIdx.x] = incl;
+  tile_sum_out(size, tmp, tile_sums);
 }
 
 template <bool kLog>
-__global__ __launch_bounds__(kLogTile) void kafka_side_emit(const uint8_t* arena, uint64_t arena_bytes,
-                                                            const uint64_t* offs, uint64_t n, const int32_t* verdicts,
-                                                            uint8_t* out, uint64_t cap, uint64_t* out_offs,
-                                                            const uint64_t* tile_base, const uint64_t* total) {
-  __shared__ uint64_t tmp[kLogTile];
+__global__ __launch_bounds__(kTileThreads) void kafka_side_emit(const uint8_t* arena, uint64_t arena_bytes,
+                                                                const uint64_t* offs, uint64_t n,
+                                                                const int32_t* verdicts, uint8_t* out, uint64_t cap,
+                                                                uint64_t* out_offs, const uint64_t* tile_base,
+                                                                const uint64_t* total) {
+  __shared__ uint64_t tmp[kTileThreads];
   __shared__ uint32_t crc_tab[256];
-  ks_crc_fill(crc_tab);  // visible after the barriers of block_inclusive
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kLogTile + threadIdx.x;
+  ks_crc_fill(crc_tab);  // visible after tile_exclusive: its contract promises a barrier
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
   const uint64_t size = i < n ? out_offs[i] : 0;  // the measure pass left the sizes here
-  const uint64_t eoff = tile_base[blockIdx.x] + block_inclusive(size, tmp) - size;
+  const uint64_t eoff = tile_exclusive(size, tmp, tile_base);
   const uint64_t all = *total;
   if (i < n) out_offs[i] = eoff;
   if (i + 1 == n) out_offs[n] = all;
   if (all > cap) return;  // uniform: the output stays untouched
   if (!size) return;
   // the measure pass validated this lane's request and walked it to the end
-  const KsGlobalSrc src{arena};
+  const ByteSrc src{arena};
   const uint64_t off = offs[i];
   uint64_t len = 0;
   if (!kafka_rec(src, arena_bytes, off, &len)) return;
@@ -148,7 +144,7 @@ __global__ __launch_bounds__(kLogTile) void kafka_side_emit(const uint8_t* arena
     KsLogEmit e{reinterpret_cast<l7m_kafka_log_record*>(out) + eoff, size, i, verdicts[i]};
     kafka_walk(src, off, len, KsCrcLds{crc_tab}, h, e);
   } else {
-    KafkaRespEmit<KsGlobalSrc, KsRespSink> e(src, KsRespSink(out + eoff, size), size);
+    KafkaRespEmit<ByteSrc, KsRespSink> e(src, KsRespSink(out + eoff, size), size);
     kafka_walk(src, off, len, KsCrcLds{crc_tab}, h, e);
     e.k.finish();
   }
@@ -163,20 +159,16 @@ hipError_t launch_kafka_side_as(const uint8_t* arena, uint64_t arena_bytes, cons
     if (e == hipSuccess && out_offs) e = hipMemsetAsync(out_offs, 0, sizeof(uint64_t), stream);
     return e;
   }
-  const uint64_t tiles = (n + kLogTile - 1) / kLogTile;
-  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
-  void* scratch = nullptr;
-  hipError_t e = scratch_alloc_async(&scratch, tiles * sizeof(uint64_t), stream);
-  if (e != hipSuccess) return e;
-  uint64_t* tile_sums = static_cast<uint64_t*>(scratch);
-  kafka_side_measure<kLog><<<dim3(static_cast<uint32_t>(tiles)), dim3(kLogTile), 0, stream>>>(
-      arena, arena_bytes, offs, n, verdicts, select, out_offs, tile_sums);
-  http_wire_scan_tiles<<<dim3(1), dim3(kScanThreads), 0, stream>>>(tile_sums, tiles, total);
-  kafka_side_emit<kLog><<<dim3(static_cast<uint32_t>(tiles)), dim3(kLogTile), 0, stream>>>(
-      arena, arena_bytes, offs, n, verdicts, out, cap, out_offs, tile_sums, total);
-  e = hipGetLastError();
-  const hipError_t f = hipFreeAsync(scratch, stream);
-  return e != hipSuccess ? e : f;
+  return tile_pipeline(
+      n, {total}, 0, stream,
+      [&](uint32_t tiles, uint64_t* tile_sums, void*) {
+        kafka_side_measure<kLog><<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(arena, arena_bytes, offs, n, verdicts,
+                                                                                 select, out_offs, tile_sums);
+      },
+      [&](uint32_t tiles, const uint64_t* tile_base, void*) {
+        kafka_side_emit<kLog><<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(arena, arena_bytes, offs, n, verdicts,
+                                                                              out, cap, out_offs, tile_base, total);
+      });
 }
 
 }  // namespace

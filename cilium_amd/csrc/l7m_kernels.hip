@@ -171,10 +171,10 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
 
 }  // namespace l7m
 
-// The HTTP/1.x wire decoder's kernels and launch_http_wire: same code object.
+// The tile pipelines (l7m_tile_scan.h), same code object: HTTP wire decoder and access log;
 #include "l7m_http_wire.hip"
 #include "l7m_http_log.hip"
-// The Kafka deny-response and log-record encoders (LogOutSink, the tile scan).
+// the Kafka deny-response and log-record encoders (l7m_http_log.hip's LogOutSink);
 #include "l7m_kafka_side.hip"
-// Connection byte streams -> head slices / Kafka records (the tile scan).
+// connection byte streams -> head slices / Kafka records.
 #include "l7m_stream_frame.hip"

@@ -5,10 +5,10 @@
 //
 // Work is sequential inside a connection and independent across connections:
 // a workgroup owns a tile of kTileThreads consecutive connections, one per
-// lane.
+// lane.  Two measure / scan / emit pipelines on l7m_tile_scan.h's scaffold.
 //   count: each lane walks its connection; status, consumed bytes, its number
 //          of slices (Kafka: and of padded arena bytes), the tile's sums
-//   scan:  exclusive sum of the tile sums (l7m_tile_scan.h), the totals
+//   scan:  exclusive sum of the tile sums, the totals (Kafka: two scans)
 //   emit:  when the totals fit the capacities each lane walks its connection
 //          again and writes its slices at tile base + sum inside the tile + k
 //   copy:  (Kafka) balanced over the arena, not over records: a thread takes
@@ -31,27 +31,6 @@
 namespace l7m {
 namespace {
 
-struct SfGlobalSrc {
-  const uint8_t* p;
-  __device__ uint8_t at(uint64_t i) const { return p[i]; }
-};
-
-// Connection c of the tile, clamped to the wire: wire[lo, hi).
-struct ConnRange {
-  uint64_t lo, hi;
-};
-
-__device__ __forceinline__ ConnRange conn_range(const uint64_t* conn_offs, uint64_t c, uint64_t n, uint64_t wire_bytes) {
-  ConnRange r{0, 0};
-  if (c < n) {
-    const uint64_t a = conn_offs[c], b = conn_offs[c + 1];
-    r.lo = a < wire_bytes ? a : wire_bytes;
-    r.hi = b < wire_bytes ? b : wire_bytes;
-    if (r.hi < r.lo) r.hi = r.lo;
-  }
-  return r;
-}
-
 __global__ __launch_bounds__(kTileThreads) void stream_http_count(const uint8_t* wire, uint64_t wire_bytes,
                                                                   const uint64_t* conn_offs, uint64_t n,
                                                                   int32_t* conn_status, uint64_t* conn_consumed,
@@ -60,15 +39,14 @@ __global__ __launch_bounds__(kTileThreads) void stream_http_count(const uint8_t*
   const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
   uint64_t cnt = 0;
   if (c < n) {
-    const ConnRange r = conn_range(conn_offs, c, n, wire_bytes);
+    const ClampedRange r = clamped_range(conn_offs, c, n, wire_bytes);
     uint64_t used = 0;
-    const int32_t st = http_stream_walk(SfGlobalSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t) { ++cnt; });
+    const int32_t st = http_stream_walk(ByteSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t) { ++cnt; });
     conn_status[c] = st;
     conn_consumed[c] = used;
     counts[c] = static_cast<uint32_t>(cnt);  // <= (hi - lo) / 16 + 1
   }
-  const uint64_t incl = block_inclusive(cnt, tmp);
-  if (threadIdx.x == kTileThreads - 1) tile_sums[blockIdx.x] = incl;
+  tile_sum_out(cnt, tmp, tile_sums);
 }
 
 __global__ __launch_bounds__(kTileThreads) void stream_http_emit(const uint8_t* wire, uint64_t wire_bytes,
@@ -81,17 +59,17 @@ __global__ __launch_bounds__(kTileThreads) void stream_http_emit(const uint8_t* 
   __shared__ uint64_t tmp[kTileThreads];
   const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
   const uint64_t cnt = c < n ? counts[c] : 0;
-  const uint64_t base = tile_base[blockIdx.x] + block_inclusive(cnt, tmp) - cnt;
+  const uint64_t base = tile_exclusive(cnt, tmp, tile_base);
   const uint64_t all = *total;
   if (all > cap || !head_offs) return;  // uniform: the per-head arrays stay untouched
   if (c >= n) return;
-  const ConnRange r = conn_range(conn_offs, c, n, wire_bytes);
+  const ClampedRange r = clamped_range(conn_offs, c, n, wire_bytes);
   if (c + 1 == n) head_offs[all] = r.hi;
   if (!cnt) return;
   l7m_http_wire_meta m{0, 0, 0, 1, {0, 0, 0}};  // no metadata: zeros, ingress
   if (conn_meta) m = conn_meta[c];
   uint64_t used = 0, k = 0;
-  http_stream_walk(SfGlobalSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t start) {
+  http_stream_walk(ByteSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t start) {
     if (k < cnt) {  // never more than the count pass counted
       head_offs[base + k] = r.lo + start;
       head_conn[base + k] = static_cast<uint32_t>(c);
@@ -114,9 +92,9 @@ __global__ __launch_bounds__(kTileThreads) void stream_kafka_count(const uint8_t
   const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
   uint64_t cnt = 0, bytes = 0;
   if (c < n) {
-    const ConnRange r = conn_range(conn_offs, c, n, wire_bytes);
+    const ClampedRange r = clamped_range(conn_offs, c, n, wire_bytes);
     uint64_t used = 0;
-    const int32_t st = kafka_stream_walk(SfGlobalSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t, uint64_t frame) {
+    const int32_t st = kafka_stream_walk(ByteSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t, uint64_t frame) {
       ++cnt;
       bytes += stream_padded(frame);
     });
@@ -125,11 +103,9 @@ __global__ __launch_bounds__(kTileThreads) void stream_kafka_count(const uint8_t
     counts[c] = static_cast<uint32_t>(cnt);  // <= (hi - lo) / 12
     sizes[c] = bytes;
   }
-  const uint64_t incl = block_inclusive(cnt, tmp);
-  if (threadIdx.x == kTileThreads - 1) tile_recs[blockIdx.x] = incl;
-  __syncthreads();
-  const uint64_t incl_b = block_inclusive(bytes, tmp);
-  if (threadIdx.x == kTileThreads - 1) tile_bytes[blockIdx.x] = incl_b;
+  tile_sum_out(cnt, tmp, tile_recs);
+  __syncthreads();  // before tmp is written again
+  tile_sum_out(bytes, tmp, tile_bytes);
 }
 
 __global__ __launch_bounds__(kTileThreads) void stream_kafka_emit(
@@ -141,15 +117,15 @@ __global__ __launch_bounds__(kTileThreads) void stream_kafka_emit(
   const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
   const uint64_t cnt = c < n ? counts[c] : 0;
   const uint64_t bytes = c < n ? sizes[c] : 0;
-  const uint64_t base = tile_recs[blockIdx.x] + block_inclusive(cnt, tmp) - cnt;
-  __syncthreads();
-  uint64_t off = tile_bytes[blockIdx.x] + block_inclusive(bytes, tmp) - bytes;
+  const uint64_t base = tile_exclusive(cnt, tmp, tile_recs);
+  __syncthreads();  // before tmp is written again
+  uint64_t off = tile_exclusive(bytes, tmp, tile_bytes);
   if (*n_recs > cap_recs || *n_recs > src_cap || *arena_bytes > cap_bytes) return;  // uniform: nothing per record
   if (!cnt) return;
-  const ConnRange r = conn_range(conn_offs, c, n, wire_bytes);
+  const ClampedRange r = clamped_range(conn_offs, c, n, wire_bytes);
   const uint32_t id = conn_identity ? conn_identity[c] : 0u;
   uint64_t used = 0, k = 0;
-  kafka_stream_walk(SfGlobalSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t start, uint64_t frame) {
+  kafka_stream_walk(ByteSrc{wire + r.lo}, r.hi - r.lo, &used, [&](uint64_t start, uint64_t frame) {
     if (k < cnt) {  // never more than the count pass counted
       rec_offsets[base + k] = off;
       rec_conn[base + k] = static_cast<uint32_t>(c);
@@ -252,22 +228,17 @@ hipError_t launch_http_stream_frame(const uint8_t* wire, uint64_t wire_bytes, co
       e = hipMemcpyAsync(head_offs, conn_offs, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream);
     return e;
   }
-  const uint64_t tiles = (n + kTileThreads - 1) / kTileThreads;
-  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
-  void* scratch = nullptr;
-  hipError_t e = scratch_alloc_async(&scratch, tiles * sizeof(uint64_t) + n * sizeof(uint32_t), stream);
-  if (e != hipSuccess) return e;
-  uint64_t* tile_sums = static_cast<uint64_t*>(scratch);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(tile_sums + tiles);
-  const dim3 grid(static_cast<uint32_t>(tiles)), block(kTileThreads);
-  stream_http_count<<<grid, block, 0, stream>>>(wire, wire_bytes, conn_offs, n, conn_status, conn_consumed, counts,
-                                                tile_sums);
-  http_wire_scan_tiles<<<dim3(1), dim3(kScanThreads), 0, stream>>>(tile_sums, tiles, total);
-  stream_http_emit<<<grid, block, 0, stream>>>(wire, wire_bytes, conn_offs, n, conn_meta, head_offs, head_conn,
-                                               head_meta, cap, counts, tile_sums, total);
-  e = hipGetLastError();
-  const hipError_t f = hipFreeAsync(scratch, stream);
-  return e != hipSuccess ? e : f;
+  return tile_pipeline(  // beside the tile sums: counts, u32[n]
+      n, {total}, n * sizeof(uint32_t), stream,
+      [&](uint32_t tiles, uint64_t* tile_sums, void* counts) {
+        stream_http_count<<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(
+            wire, wire_bytes, conn_offs, n, conn_status, conn_consumed, static_cast<uint32_t*>(counts), tile_sums);
+      },
+      [&](uint32_t tiles, const uint64_t* tile_base, void* counts) {
+        stream_http_emit<<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(
+            wire, wire_bytes, conn_offs, n, conn_meta, head_offs, head_conn, head_meta, cap,
+            static_cast<const uint32_t*>(counts), tile_base, total);
+      });
 }
 
 hipError_t launch_kafka_stream_frame(const uint8_t* wire, uint64_t wire_bytes, const uint64_t* conn_offs, uint64_t n,
@@ -281,40 +252,34 @@ hipError_t launch_kafka_stream_frame(const uint8_t* wire, uint64_t wire_bytes, c
     return e;
   }
   if (wire_bytes >> kSrcShift) return hipErrorInvalidValue;
-  const uint64_t tiles = (n + kTileThreads - 1) / kTileThreads;
-  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
   // what ascending offsets can yield, and no more than the caller's arrays hold
   const uint64_t bound = wire_bytes / 12;
   const uint64_t src_cap = cap_recs < bound ? cap_recs : bound;
-  void* scratch = nullptr;
-  hipError_t e = scratch_alloc_async(
-      &scratch, (2 * tiles + n + src_cap) * sizeof(uint64_t) + n * sizeof(uint32_t), stream);
-  if (e != hipSuccess) return e;
-  uint64_t* tile_recs = static_cast<uint64_t*>(scratch);
-  uint64_t* tile_bytes = tile_recs + tiles;
-  uint64_t* sizes = tile_bytes + tiles;
-  uint64_t* src = sizes + n;
-  uint32_t* counts = reinterpret_cast<uint32_t*>(src + src_cap);
-  const dim3 grid(static_cast<uint32_t>(tiles)), block(kTileThreads);
-  stream_kafka_count<<<grid, block, 0, stream>>>(wire, wire_bytes, conn_offs, n, conn_status, conn_consumed, counts,
-                                                 sizes, tile_recs, tile_bytes);
-  http_wire_scan_tiles<<<dim3(1), dim3(kScanThreads), 0, stream>>>(tile_recs, tiles, n_recs);
-  http_wire_scan_tiles<<<dim3(1), dim3(kScanThreads), 0, stream>>>(tile_bytes, tiles, arena_bytes);
-  stream_kafka_emit<<<grid, block, 0, stream>>>(wire, wire_bytes, conn_offs, n, conn_identity, rec_offsets, rec_conn,
-                                                src_identities, cap_recs, cap_bytes, counts, sizes, tile_recs,
-                                                tile_bytes, src, src_cap, n_recs, arena_bytes);
-  // the copy's grid from the capacity (the total is on the device): 16-byte units, at most 2048 workgroups
-  const uint64_t abound = wire_bytes + wire_bytes / 4;
-  const uint64_t units = ((cap_bytes < abound ? cap_bytes : abound) + 15) >> 4;
-  if (units && src_cap) {
-    uint64_t blocks = (units + kTileThreads - 1) / kTileThreads;
-    if (blocks > 2048) blocks = 2048;
-    stream_kafka_copy<<<dim3(static_cast<uint32_t>(blocks)), block, 0, stream>>>(
-        wire, wire_bytes, arena, cap_recs, cap_bytes, rec_offsets, src, src_cap, n_recs, arena_bytes);
-  }
-  e = hipGetLastError();
-  const hipError_t f = hipFreeAsync(scratch, stream);
-  return e != hipSuccess ? e : f;
+  // two columns of tile sums (records, arena bytes); behind them sizes, u64[n]; src, u64[src_cap]; counts, u32[n]
+  return tile_pipeline(
+      n, {n_recs, arena_bytes}, (n + src_cap) * sizeof(uint64_t) + n * sizeof(uint32_t), stream,
+      [&](uint32_t tiles, uint64_t* tile_sums, void* rest) {
+        uint64_t *sizes = static_cast<uint64_t*>(rest), *src = sizes + n;
+        uint32_t* counts = reinterpret_cast<uint32_t*>(src + src_cap);
+        stream_kafka_count<<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(
+            wire, wire_bytes, conn_offs, n, conn_status, conn_consumed, counts, sizes, tile_sums, tile_sums + tiles);
+      },
+      [&](uint32_t tiles, const uint64_t* tile_base, void* rest) {
+        uint64_t *sizes = static_cast<uint64_t*>(rest), *src = sizes + n;
+        uint32_t* counts = reinterpret_cast<uint32_t*>(src + src_cap);
+        stream_kafka_emit<<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(
+            wire, wire_bytes, conn_offs, n, conn_identity, rec_offsets, rec_conn, src_identities, cap_recs, cap_bytes,
+            counts, sizes, tile_base, tile_base + tiles, src, src_cap, n_recs, arena_bytes);
+        // the copy's grid from the capacity (the total is on the device): 16-byte units, at most 2048 workgroups
+        const uint64_t abound = wire_bytes + wire_bytes / 4;
+        const uint64_t units = ((cap_bytes < abound ? cap_bytes : abound) + 15) >> 4;
+        if (units && src_cap) {
+          uint64_t blocks = (units + kTileThreads - 1) / kTileThreads;
+          if (blocks > 2048) blocks = 2048;
+          stream_kafka_copy<<<dim3(static_cast<uint32_t>(blocks)), dim3(kTileThreads), 0, stream>>>(
+              wire, wire_bytes, arena, cap_recs, cap_bytes, rec_offsets, src, src_cap, n_recs, arena_bytes);
+        }
+      });
 }
 
 }  // namespace l7m
