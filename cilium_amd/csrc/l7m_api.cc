@@ -715,6 +715,49 @@ int l7m_kafka_stream_frame_device(const void* d_wire, size_t wire_bytes, const v
   return status_of(e);
 }
 
+int l7m_http_stream_frame_resume_device(const void* d_wire, size_t wire_bytes, const void* d_conn_offs,
+                                        size_t n_conns, const void* d_conn_meta, void* d_head_offs,
+                                        void* d_head_conn, void* d_head_meta, size_t cap_heads, void* d_conn_status,
+                                        void* d_conn_consumed, void* d_n_heads, const void* d_conn_state_in,
+                                        void* d_conn_state_out, void* hip_stream) {
+  if (!d_n_heads || !d_conn_offs || (n_conns && (!d_conn_status || !d_conn_consumed || !d_conn_state_out)) ||
+      (wire_bytes && !d_wire) || (cap_heads && (!d_head_offs || !d_head_conn)) || n_conns > 0xffffffffull)
+    return L7M_EINVAL;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
+  const hipError_t e = launch_http_stream_frame_resume(
+      static_cast<const uint8_t*>(d_wire), wire_bytes, static_cast<const uint64_t*>(d_conn_offs), n_conns,
+      static_cast<const l7m_http_wire_meta*>(d_conn_meta), static_cast<uint64_t*>(d_head_offs),
+      static_cast<uint32_t*>(d_head_conn), static_cast<l7m_http_wire_meta*>(d_head_meta), cap_heads,
+      static_cast<int32_t*>(d_conn_status), static_cast<uint64_t*>(d_conn_consumed),
+      static_cast<uint64_t*>(d_n_heads), static_cast<const l7m_stream_state*>(d_conn_state_in),
+      static_cast<l7m_stream_state*>(d_conn_state_out), static_cast<hipStream_t>(hip_stream));
+  return status_of(e);
+}
+
+int l7m_stream_carry_device(const void* d_wire, size_t wire_bytes, const void* d_conn_offs, size_t n_prev,
+                            const void* d_conn_status, const void* d_conn_consumed, const void* d_seg,
+                            size_t seg_bytes, const void* d_seg_offs, size_t n_conns, void* d_conn_state,
+                            void* d_next_wire, size_t cap_bytes, void* d_next_conn_offs, void* d_next_bytes,
+                            void* hip_stream) {
+  if (!d_next_bytes || !d_seg_offs || n_prev > n_conns ||
+      (n_prev && (!d_conn_offs || !d_conn_status || !d_conn_consumed)) || (wire_bytes && !d_wire) ||
+      (seg_bytes && !d_seg) || (cap_bytes && (!d_next_wire || !d_next_conn_offs)) || n_conns > 0xffffffffull)
+    return L7M_EINVAL;
+  // the copy kernel stores 16-byte units
+  if (reinterpret_cast<uintptr_t>(d_next_wire) & 15) return L7M_EINVAL;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
+  const hipError_t e = launch_stream_carry(
+      static_cast<const uint8_t*>(d_wire), wire_bytes, static_cast<const uint64_t*>(d_conn_offs), n_prev,
+      static_cast<const int32_t*>(d_conn_status), static_cast<const uint64_t*>(d_conn_consumed),
+      static_cast<const uint8_t*>(d_seg), seg_bytes, static_cast<const uint64_t*>(d_seg_offs), n_conns,
+      static_cast<l7m_stream_state*>(d_conn_state), static_cast<uint8_t*>(d_next_wire), cap_bytes,
+      static_cast<uint64_t*>(d_next_conn_offs), static_cast<uint64_t*>(d_next_bytes),
+      static_cast<hipStream_t>(hip_stream));
+  return status_of(e);
+}
+
 int l7m_http_access_log_device(const void* d_arena, size_t arena_bytes, const void* d_rec_offsets, size_t n,
                                const void* d_verdicts, const l7m_access_log_opts* opts, uint32_t select, void* d_out,
                                size_t cap, void* d_entry_offs, void* d_total, void* hip_stream) {

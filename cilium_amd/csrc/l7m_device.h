@@ -161,6 +161,21 @@ hipError_t launch_kafka_stream_frame(const uint8_t* wire, uint64_t wire_bytes, c
                                      uint64_t* rec_offsets, uint32_t* rec_conn, uint32_t* src_identities,
                                      uint64_t cap_recs, int32_t* conn_status, uint64_t* conn_consumed,
                                      uint64_t* n_recs, uint64_t* arena_bytes, hipStream_t stream);
+// Streaming across calls (l7m_stream_frame.hip): the HTTP framer with a state
+// per connection (state_out may alias state_in), and the next round's wire
+// from the tails and the new segments: measure, scan, emit and a copy kernel.
+// *total is always written; nothing else of the carry when it exceeds cap_bytes.
+hipError_t launch_http_stream_frame_resume(const uint8_t* wire, uint64_t wire_bytes, const uint64_t* conn_offs,
+                                           uint64_t n, const l7m_http_wire_meta* conn_meta, uint64_t* head_offs,
+                                           uint32_t* head_conn, l7m_http_wire_meta* head_meta, uint64_t cap,
+                                           int32_t* conn_status, uint64_t* conn_consumed, uint64_t* total,
+                                           const l7m_stream_state* state_in, l7m_stream_state* state_out,
+                                           hipStream_t stream);
+hipError_t launch_stream_carry(const uint8_t* wire, uint64_t wire_bytes, const uint64_t* conn_offs, uint64_t n_prev,
+                               const int32_t* conn_status, const uint64_t* conn_consumed, const uint8_t* seg,
+                               uint64_t seg_bytes, const uint64_t* seg_offs, uint64_t n, l7m_stream_state* state,
+                               uint8_t* next_wire, uint64_t cap_bytes, uint64_t* next_conn_offs, uint64_t* total,
+                               hipStream_t stream);
 
 // Mailbox of a resident evaluator (l7m_kafka.hip kafka_resident_kernel),
 // in pinned, device-mapped host memory.  The host fills slot seq %

@@ -192,4 +192,192 @@ L7M_WIRE_FN int32_t kafka_stream_walk(const Src& s, uint64_t len, uint64_t* cons
 
 L7M_WIRE_FN uint64_t stream_padded(uint64_t frame_bytes) { return (frame_bytes + 3u) & ~static_cast<uint64_t>(3); }
 
+// ---- streaming across calls (DESIGN.md "Streaming across calls") ----------
+
+L7M_WIRE_FN int32_t stream_close(l7m_stream_state& st, int32_t status) {
+  st.left = 0;
+  st.mode = L7M_STREAM_MODE_CLOSED;
+  st.status = status;
+  return status;
+}
+
+L7M_WIRE_FN int32_t stream_pause(l7m_stream_state& st, int32_t mode, uint64_t left, int32_t status) {
+  st.left = left;
+  st.mode = mode;
+  st.status = 0;
+  return status;
+}
+
+// http_stream_walk made resumable: the connection s[0, len) is entered in
+// state `st` (what an earlier walk over the bytes in front of it left) and
+// `st` receives the state it is left in.  f(start) per head wire_scan accepts
+// or refuses, never for an incomplete one; *consumed is how far the walk has
+// committed: a complete head is consumed when it is emitted and a body as it
+// is skipped, so that wire[consumed, len) and the state are all a later walk
+// needs.  The byte rules are http_stream_walk's and stream_chunked's, examined
+// in the same order; a chunk-size line or a trailer line that the bytes end
+// in is read again from its first byte.
+template <class Src, class F>
+L7M_WIRE_FN int32_t http_stream_walk_resume(const Src& s, uint64_t len, l7m_stream_state& st, uint64_t* consumed,
+                                            F&& f) {
+  int32_t mode = st.mode;
+  uint64_t left = st.left;
+  if (static_cast<uint32_t>(mode) >= static_cast<uint32_t>(L7M_STREAM_MODE_CLOSED)) {  // CLOSED, or no mode at all
+    *consumed = len;
+    return st.status;
+  }
+  uint64_t p = 0;
+  *consumed = 0;
+  for (;;) {
+    if (mode == L7M_STREAM_MODE_HEAD) {
+      if (p >= len) return stream_pause(st, L7M_STREAM_MODE_HEAD, 0, L7M_STREAM_OK);
+      const StreamAt<Src> h{s, p};
+      WireInfo info;
+      wire_scan(h, len - p, info);
+      if (info.status == L7M_WIRE_EINCOMPLETE) return stream_pause(st, L7M_STREAM_MODE_HEAD, 0, L7M_STREAM_EPARTIAL_HEAD);
+      f(p);
+      if (info.status < 0) return stream_close(st, L7M_STREAM_EBADHEAD);
+      const uint64_t body = p + static_cast<uint64_t>(info.status);
+      if (info.mlen == 7 && h.at(0) == 'C' && h.at(1) == 'O' && h.at(2) == 'N' && h.at(3) == 'N' && h.at(4) == 'E' &&
+          h.at(5) == 'C' && h.at(6) == 'T') {
+        *consumed = body;  // the head; what follows is the tunnel's
+        return stream_close(st, L7M_STREAM_TUNNEL);
+      }
+      uint32_t n_te = 0, n_cl = 0;
+      uint64_t te_pos = 0, te_len = 0, cl_pos = 0, cl_len = 0;
+      wire_lines(h, info, [&](uint64_t n0, uint64_t nlen, uint64_t v0, uint64_t vlen) {
+        if (stream_ieq(h, n0, nlen, "transfer-encoding", 17)) {
+          ++n_te;
+          te_pos = v0;
+          te_len = vlen;
+        } else if (stream_ieq(h, n0, nlen, "content-length", 14)) {
+          ++n_cl;
+          cl_pos = v0;
+          cl_len = vlen;
+        }
+      });
+      if (n_te && n_cl) return stream_close(st, L7M_STREAM_EAMBIGUOUS);
+      if (n_te) {
+        if (n_te != 1 || !stream_ieq(h, te_pos, te_len, "chunked", 7)) return stream_close(st, L7M_STREAM_EBADTE);
+        mode = L7M_STREAM_MODE_CHUNK_LINE;
+      } else if (n_cl) {
+        if (n_cl != 1 || cl_len < 1 || cl_len > 18) return stream_close(st, L7M_STREAM_EBADLENGTH);
+        uint64_t v = 0;
+        for (uint64_t i = 0; i < cl_len; ++i) {
+          const uint32_t c = h.at(cl_pos + i);
+          if (c - '0' >= 10u) return stream_close(st, L7M_STREAM_EBADLENGTH);
+          v = v * 10u + (c - '0');  // < 10^18
+        }
+        left = v;
+        if (v) mode = L7M_STREAM_MODE_BODY;
+      }
+      p = body;
+      *consumed = p;
+    } else if (mode == L7M_STREAM_MODE_BODY || mode == L7M_STREAM_MODE_CHUNK_DATA) {
+      const uint64_t k = left < len - p ? left : len - p;
+      p += k;
+      left -= k;
+      *consumed = p;
+      if (left) return stream_pause(st, mode, left, L7M_STREAM_EPARTIAL_BODY);
+      if (mode == L7M_STREAM_MODE_BODY) {
+        mode = L7M_STREAM_MODE_HEAD;
+        continue;
+      }
+      // the CRLF behind the chunk's data
+      if (p >= len) return stream_pause(st, mode, 0, L7M_STREAM_EPARTIAL_BODY);
+      if (s.at(p) != '\r') return stream_close(st, L7M_STREAM_EBADCHUNK);
+      if (p + 1 >= len) return stream_pause(st, mode, 0, L7M_STREAM_EPARTIAL_BODY);
+      if (s.at(p + 1) != '\n') return stream_close(st, L7M_STREAM_EBADCHUNK);
+      p += 2;
+      *consumed = p;
+      mode = L7M_STREAM_MODE_CHUNK_LINE;
+    } else if (mode == L7M_STREAM_MODE_CHUNK_LINE) {
+      uint64_t q = p, size = 0;
+      uint32_t nd = 0;
+      for (;; ++q) {
+        if (q >= len) return stream_pause(st, mode, 0, L7M_STREAM_EPARTIAL_BODY);
+        const int32_t x = stream_hex(s.at(q));
+        if (x < 0) break;
+        if (nd == 15) return stream_close(st, L7M_STREAM_EBADCHUNK);  // a 16th digit
+        size = size << 4 | static_cast<uint64_t>(x);
+        ++nd;
+      }
+      if (nd == 0) return stream_close(st, L7M_STREAM_EBADCHUNK);
+      uint32_t c = s.at(q);
+      if (c == ';') {
+        for (++q;; ++q) {
+          if (q >= len) return stream_pause(st, mode, 0, L7M_STREAM_EPARTIAL_BODY);
+          c = s.at(q);
+          if (c == '\r') break;
+          if (c == '\n' || c == 0) return stream_close(st, L7M_STREAM_EBADCHUNK);
+        }
+      }
+      if (c != '\r') return stream_close(st, L7M_STREAM_EBADCHUNK);
+      if (++q >= len) return stream_pause(st, mode, 0, L7M_STREAM_EPARTIAL_BODY);
+      if (s.at(q) != '\n') return stream_close(st, L7M_STREAM_EBADCHUNK);
+      p = q + 1;
+      *consumed = p;
+      left = size;
+      mode = size ? L7M_STREAM_MODE_CHUNK_DATA : L7M_STREAM_MODE_TRAILER;
+    } else {  // TRAILER: one line (the head's header-line byte rules, no length limits) or the empty line
+      uint64_t q = p;
+      if (q >= len) return stream_pause(st, mode, 0, L7M_STREAM_EPARTIAL_BODY);
+      uint32_t c = s.at(q);
+      if (c == '\r') {
+        if (++q >= len) return stream_pause(st, mode, 0, L7M_STREAM_EPARTIAL_BODY);
+        if (s.at(q) != '\n') return stream_close(st, L7M_STREAM_EBADCHUNK);
+        mode = L7M_STREAM_MODE_HEAD;
+      } else {
+        while (q < len && wire_tchar(s.at(q))) ++q;
+        if (q >= len) return stream_pause(st, mode, 0, L7M_STREAM_EPARTIAL_BODY);
+        if (q == p || s.at(q) != ':') return stream_close(st, L7M_STREAM_EBADCHUNK);
+        for (++q;; ++q) {
+          if (q >= len) return stream_pause(st, mode, 0, L7M_STREAM_EPARTIAL_BODY);
+          c = s.at(q);
+          if (c == '\r') break;
+          if (c == '\n' || c == 0) return stream_close(st, L7M_STREAM_EBADCHUNK);
+        }
+        if (++q >= len) return stream_pause(st, mode, 0, L7M_STREAM_EPARTIAL_BODY);
+        if (s.at(q) != '\n') return stream_close(st, L7M_STREAM_EBADCHUNK);
+      }
+      p = q + 1;
+      *consumed = p;
+    }
+  }
+}
+
+// What l7m_stream_carry takes from connection c: the tail wire[tsrc, tsrc +
+// tlen), then seg[nsrc, nsrc + nlen), after `skip` body bytes of the segment
+// were dropped.  [lo, hi) is the connection in the wire (empty for one opened
+// this round), [slo, shi) its segment, (mode, left) its state: zeros for Kafka,
+// which carries like a connection at a request boundary.
+struct CarryPlan {
+  uint64_t tsrc, tlen, nsrc, nlen, skip;
+};
+
+L7M_WIRE_FN CarryPlan stream_carry_plan(uint64_t lo, uint64_t hi, uint64_t consumed, int32_t status, uint64_t slo,
+                                        uint64_t shi, int32_t mode, uint64_t left) {
+  CarryPlan pl{0, 0, 0, 0, 0};
+  const bool open = status == L7M_STREAM_OK || status == L7M_STREAM_EPARTIAL_HEAD ||
+                    status == L7M_STREAM_EPARTIAL_BODY || status == L7M_STREAM_EPARTIAL_FRAME;
+  if (!open || static_cast<uint32_t>(mode) >= static_cast<uint32_t>(L7M_STREAM_MODE_CLOSED)) return pl;
+  pl.nsrc = slo;
+  pl.nlen = shi - slo;
+  if ((mode == L7M_STREAM_MODE_BODY || mode == L7M_STREAM_MODE_CHUNK_DATA) && left) {
+    pl.skip = left < pl.nlen ? left : pl.nlen;  // the tail is empty by the framer's contract
+    pl.nsrc += pl.skip;
+    pl.nlen -= pl.skip;
+    return pl;
+  }
+  pl.tsrc = lo + consumed;
+  pl.tlen = hi - lo - consumed;
+  return pl;
+}
+
+L7M_WIRE_FN void stream_carry_state(l7m_stream_state& st, uint64_t skip) {
+  if (!skip) return;
+  st.left -= skip;
+  if (st.mode == L7M_STREAM_MODE_BODY && !st.left) st.mode = L7M_STREAM_MODE_HEAD;
+}
+
 }  // namespace l7m

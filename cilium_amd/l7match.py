@@ -62,6 +62,9 @@ LOG_FORWARDED, LOG_DENIED = 1, 2
 STREAM_OK, STREAM_TUNNEL = 0, 1
 (STREAM_EBADHEAD, STREAM_EPARTIAL_HEAD, STREAM_EAMBIGUOUS, STREAM_EBADTE, STREAM_EBADLENGTH, STREAM_EBADCHUNK,
  STREAM_EPARTIAL_BODY, STREAM_EPARTIAL_FRAME, STREAM_EBADSIZE) = -1, -2, -3, -4, -5, -6, -7, -8, -9
+# l7m_stream_state.mode (L7M_STREAM_MODE_*)
+(STREAM_MODE_HEAD, STREAM_MODE_BODY, STREAM_MODE_CHUNK_DATA, STREAM_MODE_CHUNK_LINE, STREAM_MODE_TRAILER,
+ STREAM_MODE_CLOSED) = range(6)
 
 # Every symbol include/l7match.h declares (checked by
 # tests/test_http_cpu.py::test_library_exports_every_header_symbol).
@@ -86,6 +89,8 @@ EXPORTED_SYMBOLS = (
     "l7m_http_stream_heads_bound", "l7m_http_stream_frame", "l7m_http_stream_frame_device",
     "l7m_kafka_stream_records_bound", "l7m_kafka_stream_arena_bound", "l7m_kafka_stream_frame",
     "l7m_kafka_stream_frame_device",
+    "l7m_http_stream_frame_resume", "l7m_http_stream_frame_resume_device", "l7m_stream_carry_bound",
+    "l7m_stream_carry", "l7m_stream_carry_device",
 )
 
 
@@ -335,6 +340,12 @@ def _load() -> ctypes.CDLL:
     lib.l7m_kafka_stream_frame.argtypes = [P, sz, P, sz, P, P, sz, P, P, P, sz, P, P, ctypes.POINTER(sz),
                                            ctypes.POINTER(sz)]
     lib.l7m_kafka_stream_frame_device.argtypes = [P, sz, P, sz, P, P, sz, P, P, P, sz, P, P, P, P, P]
+    lib.l7m_http_stream_frame_resume.argtypes = [P, sz, P, sz, P, P, P, P, sz, P, P, ctypes.POINTER(sz), P, P]
+    lib.l7m_http_stream_frame_resume_device.argtypes = [P, sz, P, sz, P, P, P, P, sz, P, P, P, P, P, P]
+    lib.l7m_stream_carry_bound.argtypes = [sz, sz]
+    lib.l7m_stream_carry_bound.restype = sz
+    lib.l7m_stream_carry.argtypes = [P, sz, P, sz, P, P, P, sz, P, sz, P, P, sz, P, ctypes.POINTER(ctypes.c_uint64)]
+    lib.l7m_stream_carry_device.argtypes = [P, sz, P, sz, P, P, P, sz, P, sz, P, P, sz, P, P, P]
     return lib
 
 
@@ -746,6 +757,126 @@ def frame_kafka_streams_device(d_wire, wire_bytes: int, d_conn_offs, n_conns: in
                                             stream)
     if rc != L7M_OK:
         raise L7Error(rc, "l7m_kafka_stream_frame_device failed")
+
+
+# l7m_stream_state: 16 bytes per connection, all zero = a fresh connection
+STREAM_STATE_DTYPE = np.dtype([("left", "<u8"), ("mode", "<i4"), ("status", "<i4")])
+assert STREAM_STATE_DTYPE.itemsize == 16
+
+
+def _stream_state(state, n: int) -> np.ndarray:
+    """A private, contiguous copy of `state` (None: n fresh connections)."""
+    if state is None:
+        return np.zeros(n, dtype=STREAM_STATE_DTYPE)
+    state = np.array(state, dtype=STREAM_STATE_DTYPE, copy=True)
+    assert state.shape == (n,)
+    return state
+
+
+def frame_http_streams_resume(conns, state=None, meta=None):
+    """l7m_http_stream_frame_resume (host): conns and meta as for
+    frame_http_streams, state None (all fresh) or a STREAM_STATE_DTYPE array
+    with one entry per connection (not modified).  Returns (wire, head_offs,
+    head_conn, head_meta, conn_status, conn_consumed, state_out).  Only heads
+    the decoder accepts or refuses are slices: head_offs[i] is the start of
+    head i, head_offs[-1] the end of the wire, and a slice may carry trailing
+    bytes that are not its own; decode_http_wire takes (wire, head_offs) as it is."""
+    wire, coffs = join_conns(conns)
+    nc = coffs.shape[0] - 1
+    meta = _wire_meta(meta, nc)
+    state = _stream_state(state, nc)
+    out = np.zeros(nc, dtype=STREAM_STATE_DTYPE)
+    status = np.zeros(nc, dtype=np.int32)
+    consumed = np.zeros(nc, dtype=np.uint64)
+    n = ctypes.c_size_t(0)
+    rc = _lib.l7m_http_stream_frame_resume(wire.ctypes.data, wire.nbytes, coffs.ctypes.data, nc, None, None, None,
+                                           None, 0, status.ctypes.data, consumed.ctypes.data, ctypes.byref(n),
+                                           state.ctypes.data, out.ctypes.data)
+    if rc not in (L7M_OK, L7M_ENOMEM):
+        raise L7Error(rc, "l7m_http_stream_frame_resume failed")
+    cap = n.value
+    hoffs = np.zeros(cap + 1, dtype=np.uint64)
+    hconn = np.zeros(cap, dtype=np.uint32)
+    hmeta = None if meta is None else np.zeros(cap, dtype=WIRE_META_DTYPE)
+    rc = _lib.l7m_http_stream_frame_resume(wire.ctypes.data, wire.nbytes, coffs.ctypes.data, nc,
+                                           None if meta is None else meta.ctypes.data, hoffs.ctypes.data,
+                                           hconn.ctypes.data if cap else None,
+                                           None if hmeta is None or not cap else hmeta.ctypes.data, cap,
+                                           status.ctypes.data, consumed.ctypes.data, ctypes.byref(n),
+                                           state.ctypes.data, out.ctypes.data)
+    if rc != L7M_OK or n.value != cap:
+        raise L7Error(rc, "l7m_http_stream_frame_resume failed")
+    return wire, hoffs, hconn, hmeta, status, consumed, out
+
+
+def frame_http_streams_resume_device(d_wire, wire_bytes: int, d_conn_offs, n_conns: int, d_conn_meta, d_head_offs,
+                                     d_head_conn, d_head_meta, cap_heads: int, d_conn_status, d_conn_consumed,
+                                     d_n_heads, d_conn_state_in, d_conn_state_out, stream=None) -> None:
+    """l7m_http_stream_frame_resume_device: device pointers (ints or torch
+    tensors) -> enqueue on `stream` (int handle), no synchronisation.
+    d_conn_state_in: None (all fresh) or 16 bytes per connection;
+    d_conn_state_out may be the same buffer.  d_n_heads as for
+    frame_http_streams_device."""
+    rc = _lib.l7m_http_stream_frame_resume_device(_dev_ptr(d_wire), wire_bytes, _dev_ptr(d_conn_offs), n_conns,
+                                                  _dev_ptr(d_conn_meta), _dev_ptr(d_head_offs),
+                                                  _dev_ptr(d_head_conn), _dev_ptr(d_head_meta), cap_heads,
+                                                  _dev_ptr(d_conn_status), _dev_ptr(d_conn_consumed),
+                                                  _dev_ptr(d_n_heads), _dev_ptr(d_conn_state_in),
+                                                  _dev_ptr(d_conn_state_out), stream)
+    if rc != L7M_OK:
+        raise L7Error(rc, "l7m_http_stream_frame_resume_device failed")
+
+
+def stream_carry_bound(wire_bytes: int, seg_bytes: int) -> int:
+    """l7m_stream_carry_bound: bytes the next round's wire can take."""
+    return int(_lib.l7m_stream_carry_bound(wire_bytes, seg_bytes))
+
+
+def carry_streams(conns, conn_status, conn_consumed, segs, state=None):
+    """l7m_stream_carry (host): conns is this round's connections (a sequence
+    of bytes objects or a (wire, conn_offs) pair) with the framer's conn_status
+    and conn_consumed, segs the newly arrived bytes per connection (as many as
+    conns or more: the further ones are connections opened this round), state
+    None (Kafka) or a STREAM_STATE_DTYPE array with one entry per segment (not
+    modified).  Returns ((next_wire, next_conn_offs), state_out): the pair is
+    what the framers take as conns; state_out is None without state."""
+    wire, coffs = join_conns(conns)
+    seg, soffs = join_conns(segs)
+    n_prev, nc = coffs.shape[0] - 1, soffs.shape[0] - 1
+    status = np.ascontiguousarray(conn_status, dtype=np.int32)
+    consumed = np.ascontiguousarray(conn_consumed, dtype=np.uint64)
+    assert status.shape == (n_prev,) and consumed.shape == (n_prev,)
+    if state is not None:
+        state = _stream_state(state, nc)
+    args = (wire.ctypes.data, wire.nbytes, coffs.ctypes.data, n_prev, status.ctypes.data, consumed.ctypes.data,
+            seg.ctypes.data, seg.nbytes, soffs.ctypes.data, nc, None if state is None else state.ctypes.data)
+    need = ctypes.c_uint64(0)
+    rc = _lib.l7m_stream_carry(*args, None, 0, None, ctypes.byref(need))
+    if rc not in (L7M_OK, L7M_ENOMEM):
+        raise L7Error(rc, "l7m_stream_carry failed")
+    cap = need.value
+    nwire = np.zeros(max(1, cap), dtype=np.uint8)
+    noffs = np.zeros(nc + 1, dtype=np.uint64)
+    rc = _lib.l7m_stream_carry(*args, nwire.ctypes.data, cap, noffs.ctypes.data, ctypes.byref(need))
+    if rc != L7M_OK or need.value != cap:
+        raise L7Error(rc, "l7m_stream_carry failed")
+    return (nwire[:cap], noffs), state
+
+
+def carry_streams_device(d_wire, wire_bytes: int, d_conn_offs, n_prev: int, d_conn_status, d_conn_consumed, d_seg,
+                         seg_bytes: int, d_seg_offs, n_conns: int, d_conn_state, d_next_wire, cap_bytes: int,
+                         d_next_conn_offs, d_next_bytes, stream=None) -> None:
+    """l7m_stream_carry_device: device pointers (ints or torch tensors) ->
+    enqueue on `stream`, no synchronisation.  d_conn_state: None (Kafka) or 16
+    bytes per connection, updated in place.  d_next_wire: 16-byte aligned,
+    round_up(cap_bytes, 16) bytes.  d_next_bytes: one uint64; when it ends up
+    above cap_bytes nothing else was written."""
+    rc = _lib.l7m_stream_carry_device(_dev_ptr(d_wire), wire_bytes, _dev_ptr(d_conn_offs), n_prev,
+                                      _dev_ptr(d_conn_status), _dev_ptr(d_conn_consumed), _dev_ptr(d_seg), seg_bytes,
+                                      _dev_ptr(d_seg_offs), n_conns, _dev_ptr(d_conn_state), _dev_ptr(d_next_wire),
+                                      cap_bytes, _dev_ptr(d_next_conn_offs), _dev_ptr(d_next_bytes), stream)
+    if rc != L7M_OK:
+        raise L7Error(rc, "l7m_stream_carry_device failed")
 
 
 # --------------------------------------------------------------------------

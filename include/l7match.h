@@ -525,6 +525,112 @@ int l7m_kafka_stream_frame_device(const void* d_wire, size_t wire_bytes, const v
                                   void* d_conn_consumed, void* d_n_recs /* u64 */, void* d_arena_bytes /* u64 */,
                                   void* hip_stream);
 
+/* ---- streaming across calls (DESIGN.md "Streaming across calls") ----------
+ * A proxy frames the same connections round after round as bytes arrive.  The
+ * HTTP framer below keeps 16 bytes of state per connection between rounds, and
+ * l7m_stream_carry(_device) builds the next round's wire from this round's
+ * unconsumed tails and the newly arrived bytes, so that the loop frame ->
+ * decode -> eval -> side effects -> carry -> frame never leaves the device.
+ * The Kafka framer needs no state (conn_consumed stops at a frame boundary):
+ * the one-shot framer and the carry with conn_state = NULL are its loop. */
+typedef struct l7m_stream_state { /* 16 bytes; all zero = a fresh connection */
+  uint64_t left;   /* BODY / CHUNK_DATA: bytes of the body or chunk still to skip */
+  int32_t mode;    /* L7M_STREAM_MODE_* */
+  int32_t status;  /* CLOSED: the L7M_STREAM_* code that ended the connection */
+} l7m_stream_state;
+#define L7M_STREAM_MODE_HEAD 0       /* at a request boundary */
+#define L7M_STREAM_MODE_BODY 1       /* inside a counted body, `left` bytes to go, then HEAD */
+#define L7M_STREAM_MODE_CHUNK_DATA 2 /* `left` bytes of chunk data to go (0: at the CRLF behind them) */
+#define L7M_STREAM_MODE_CHUNK_LINE 3 /* at the first byte of a chunk-size line */
+#define L7M_STREAM_MODE_TRAILER 4    /* at the first byte of a trailer line or of the closing empty line */
+#define L7M_STREAM_MODE_CLOSED 5     /* ended with `status`; yields nothing more */
+
+/* The resumable HTTP framer: l7m_http_stream_frame's arguments and capacity
+ * contract, plus the state each connection enters with (conn_state_in, NULL =
+ * all fresh) and leaves with (conn_state_out, always complete like
+ * conn_status; may alias conn_state_in).  The byte rules are the one-shot's;
+ * what differs is where a walk stops and starts again:
+ *   - a complete head is consumed when it is emitted (conn_consumed is the end
+ *     of the head, then moves through the body as it is skipped), so no head
+ *     is ever emitted twice, and a body larger than any wire is framed in
+ *     pieces: L7M_STREAM_EPARTIAL_BODY with the position kept in the state;
+ *   - an incomplete trailing head is NOT a slice: L7M_STREAM_EPARTIAL_HEAD
+ *     with conn_consumed in front of it;
+ *   - EBADHEAD, TUNNEL, EAMBIGUOUS, EBADTE, EBADLENGTH and EBADCHUNK close the
+ *     connection: state {0, CLOSED, status}.  A connection that enters CLOSED
+ *     (or with a mode outside 0..5) yields no slice, conn_consumed = its whole
+ *     length, conn_status = the state's status, and keeps its state.
+ * A slice exists only for a head the decoder accepts or refuses, so slices no
+ * longer tile the connections: head_offs[i] is the start of head i,
+ * head_offs[n_heads] = conn_offs[n_conns] (head_offs[0] with no heads), and
+ * slice i as the decoder sees it, [head_offs[i], head_offs[i+1]), may carry
+ * trailing bytes that are not its own (its body, later connections' chunk
+ * lines, an incomplete head).  That is sound because the decoder reads a head
+ * in one pass from left to right and its code for a complete or refused head
+ * is decided at or before the head's last examined byte: bytes behind it
+ * change neither the status nor the record (prefix stability).
+ * l7m_http_stream_heads_bound still bounds n_heads. */
+int l7m_http_stream_frame_resume(const uint8_t* wire, size_t wire_bytes, const uint64_t* conn_offs, size_t n_conns,
+                                 const l7m_http_wire_meta* conn_meta, uint64_t* head_offs, uint32_t* head_conn,
+                                 l7m_http_wire_meta* head_meta, size_t cap_heads, int32_t* conn_status,
+                                 uint64_t* conn_consumed, size_t* n_heads,
+                                 const l7m_stream_state* conn_state_in /* NULL or n_conns */,
+                                 l7m_stream_state* conn_state_out /* n_conns */);
+/* The same on device buffers: a count pass, a scan and an emit pass, one
+ * connection per lane, enqueued without synchronising. */
+int l7m_http_stream_frame_resume_device(const void* d_wire, size_t wire_bytes, const void* d_conn_offs,
+                                        size_t n_conns, const void* d_conn_meta, void* d_head_offs,
+                                        void* d_head_conn, void* d_head_meta, size_t cap_heads, void* d_conn_status,
+                                        void* d_conn_consumed, void* d_n_heads /* u64 */,
+                                        const void* d_conn_state_in, void* d_conn_state_out, void* hip_stream);
+
+/* The next round's wire (both protocols).  Connections keep their index;
+ * indices n_prev .. n_conns-1 are connections opened this round (no tail; the
+ * caller zeroes their state).  With T = wire[conn_offs[c] + conn_consumed[c],
+ * conn_offs[c+1]) (empty for c >= n_prev) and N = seg[seg_offs[c],
+ * seg_offs[c+1]), the next round's connection c is
+ *   - empty when conn_status[c] is not one of OK, EPARTIAL_HEAD,
+ *     EPARTIAL_BODY, EPARTIAL_FRAME, or its state's mode is CLOSED (the
+ *     connection has ended; the caller saw its status and closes it);
+ *   - N[k:] when its state's mode is BODY or CHUNK_DATA with left > 0, where
+ *     k = min(left, |N|) (T is empty then by the framer's contract); the state
+ *     gets left -= k, and a BODY that reaches 0 becomes HEAD: body bytes are
+ *     never copied into the next wire;
+ *   - T followed by N otherwise.
+ * *next_bytes (at most l7m_stream_carry_bound) is always written.  When it
+ * exceeds cap_bytes nothing else is written, the state included, and the call
+ * returns L7M_ENOMEM; a call with next_conn_offs == NULL is the sizing call and
+ * writes *next_bytes only.  L7M_EINVAL for offsets that do not ascend or that
+ * pass their buffer, conn_consumed[c] beyond its connection and
+ * n_prev > n_conns.
+ * With conn_state == NULL (Kafka) nothing remembers that a connection has
+ * ended: it is empty in the next round, where the framer reports OK for it,
+ * and bytes supplied for it after that would be framed from mid-stream.  The
+ * caller closes a connection in the round that reports its end and supplies
+ * no more bytes for its index (an empty segment).  With a state the CLOSED
+ * mode keeps an HTTP connection empty whatever arrives. */
+size_t l7m_stream_carry_bound(size_t wire_bytes, size_t seg_bytes); /* wire_bytes + seg_bytes */
+int l7m_stream_carry(const uint8_t* wire, size_t wire_bytes, const uint64_t* conn_offs /* n_prev + 1 */,
+                     size_t n_prev, const int32_t* conn_status, const uint64_t* conn_consumed /* n_prev each */,
+                     const uint8_t* seg, size_t seg_bytes, const uint64_t* seg_offs /* n_conns + 1 */,
+                     size_t n_conns /* >= n_prev */, l7m_stream_state* conn_state /* NULL or n_conns, in and out */,
+                     uint8_t* next_wire, size_t cap_bytes, uint64_t* next_conn_offs /* n_conns + 1 */,
+                     uint64_t* next_bytes);
+/* The same on device buffers, enqueued without synchronising: a measure pass,
+ * a scan, an emit pass (offsets and state) and a copy kernel balanced over the
+ * destination in 16-byte units.  d_wire and d_seg need byte alignment only;
+ * d_next_wire must be 16-byte aligned and writable up to round_up(cap_bytes,
+ * 16), since whole units are stored 16 bytes at a time; nothing at or past
+ * round_up(*d_next_bytes, 16) is written.  *d_next_bytes is a u64; when it
+ * ends up above cap_bytes nothing else was written.  Input that the host
+ * function refuses gives unspecified output, without a load outside d_wire /
+ * d_seg or a store outside the outputs. */
+int l7m_stream_carry_device(const void* d_wire, size_t wire_bytes, const void* d_conn_offs, size_t n_prev,
+                            const void* d_conn_status, const void* d_conn_consumed, const void* d_seg,
+                            size_t seg_bytes, const void* d_seg_offs, size_t n_conns, void* d_conn_state,
+                            void* d_next_wire, size_t cap_bytes, void* d_next_conn_offs,
+                            void* d_next_bytes /* u64 */, void* hip_stream);
+
 /* ---- evaluation flags ------------------------------------------------------
  * 0 for normal use. The DIAG flags select profiling ablations of the HTTP
  * kernel whose verdicts are NOT valid (used by bench.py --diag).  HTTP
