@@ -992,6 +992,50 @@ __device__ __forceinline__ uint32_t keep_scalar(uint32_t v) {
   return v;
 }
 
+// What one walk of the lean kernel needs of its automaton: the chain start
+// (LdsChain), the end code's latch list, and the candidate entries of its end
+// codes in program memory (the touch).
+struct JobDfa {
+  uint32_t e, lim, t0;              // LdsChain: start entry (0: dead from the start), first latched row, table
+  uint32_t lds_latch, start_latch;  // LdsChain::code_in_entry
+  uint32_t d;                       // the DFA's index (its end-code register)
+  uint32_t touch;                   // 1: it has candidate entries, in program memory
+  uint32_t nsets, ct_off;           // entry index of a latched code; the entries' program word offset
+};
+__device__ __forceinline__ JobDfa job_dfa(const DfaDesc& dd, uint32_t d, bool cand) {
+  LdsChain ch;
+  ch.init(dd);
+  JobDfa j;
+  j.e = dd.start_base ? ch.e : 0u;  // dead from the start: the dead row (walk_lds skips the walk: the same code, 0)
+  j.lim = ch.lim;
+  j.t0 = ch.t0;
+  j.lds_latch = dd.lds_latch;
+  j.start_latch = dd.start_latch;
+  j.d = d;
+  j.touch = cand && dd.lds_ct == kNone ? 1u : 0u;
+  j.nsets = dd.nsets;
+  j.ct_off = dd.ct_off;
+  return j;
+}
+// The JobDfa of method, path and authority -- one automaton each in a lean
+// program, so the same in every lane and tile -- as five scalars per job,
+// formed once per wave: lim < 2^17 and t0 < 2^14 (tables end below image word
+// kLdsTableWords), lds_latch < 2^17 (a u16 index into <= 160 KiB), nsets < 2^8
+// (the end code is a byte of the table entry), d < 4.
+struct LeanJob {
+  uint32_t e, lim_t0, misc, start_latch, ct_off;  // misc: lds_latch | nsets << 17 | d << 25 | touch << 27
+};
+__device__ __forceinline__ LeanJob make_lean_job(const Ctx& c, uint32_t f, uint32_t cand_dfas) {
+  const uint32_t d = c.fields[f].dfa_first;
+  const JobDfa j = job_dfa(c.dds[d], d, ((cand_dfas >> d) & 1u) != 0);
+  LeanJob l;
+  l.e = keep_scalar(j.e);
+  l.lim_t0 = keep_scalar(j.lim | j.t0 << 17);
+  l.misc = keep_scalar((j.lds_latch & 0x1ffffu) | (j.nsets & 0xffu) << 17 | (j.d & 3u) << 25 | j.touch << 27);
+  l.start_latch = keep_scalar(j.start_latch);
+  l.ct_off = keep_scalar(j.ct_off);
+  return l;
+}
 // The lean kernel's stand-in for HttpHeader in eval_walk / eval_verify: the
 // members they read carry HttpHeader's names, so either type fits.
 struct LeanHeader {
@@ -1001,8 +1045,47 @@ struct LeanHeader {
   uint32_t name_len_lo, name_len_hi, lds_name_tab, name_tab_mask;
   uint32_t cand_dfas_lo, pres_fields_lo, pres_fields_hi, always_rule;
   Span zero_list;
+  LeanJob j0, j1, j2;
+  // job J's automaton, every member a scalar
+  template <int J>
+  __device__ __forceinline__ JobDfa job() const {
+    const LeanJob& l = J == 0 ? j0 : J == 1 ? j1 : j2;
+    JobDfa j;
+    j.e = l.e;
+    j.lim = l.lim_t0 & 0x1ffffu;
+    j.t0 = l.lim_t0 >> 17;
+    j.lds_latch = l.misc & 0x1ffffu;
+    j.start_latch = l.start_latch;
+    j.d = (l.misc >> 25) & 3u;
+    j.touch = l.misc >> 27;
+    j.nsets = (l.misc >> 17) & 0xffu;
+    j.ct_off = l.ct_off;
+    return j;
+  }
 };
-__device__ __forceinline__ LeanHeader make_lean_header(const HttpHeader& h) {
+// One walk of the lean kernel: the automaton is walked from LDS and its
+// entries carry the end code.  The candidate entry (program memory) of the
+// request's first walk that selects one is touched as in the generic kernel.
+template <class Src>
+__device__ __forceinline__ void lean_walk(const Ctx& c, const JobDfa& jd, const Src& src, uint32_t p, uint32_t len,
+                                          Codes<4>& codes, bool& touched, uint32_t& pf_t, uint64_t (&prof)[8]) {
+  LdsChain ch;
+  ch.e = jd.e;
+  ch.pw = 0;
+  ch.lim = jd.lim;
+  ch.t0 = jd.t0;
+  ch.slast = kNone;
+  ch.template run<true>(src, p, len, 0);  // (field tails from one word on the LDS stage)
+  const uint32_t code = ch.code_in_entry(c.img, jd.lds_latch, jd.start_latch);
+  HPROF(3);
+  codes.set(jd.d, code);
+  if (!touched && code && jd.touch) {
+    const uint32_t idx = (code & kLatchedBit) ? jd.nsets + (code & ~kLatchedBit) : code;
+    pf_t = c.prog[jd.ct_off + 16u * idx];
+    touched = true;
+  }
+}
+__device__ __forceinline__ LeanHeader make_lean_header(const HttpHeader& h, const Ctx& c) {
   LeanHeader l;
   l.name_len_lo = keep_scalar(h.name_len_lo);
   l.name_len_hi = keep_scalar(h.name_len_hi);
@@ -1014,12 +1097,15 @@ __device__ __forceinline__ LeanHeader make_lean_header(const HttpHeader& h) {
   l.always_rule = keep_scalar(h.always_rule);
   l.zero_list.off = keep_scalar(h.zero_list.off);
   l.zero_list.len = keep_scalar(h.zero_list.len);
+  l.j0 = make_lean_job(c, 0, l.cand_dfas_lo);
+  l.j1 = make_lean_job(c, 1, l.cand_dfas_lo);
+  l.j2 = make_lean_job(c, 2, l.cand_dfas_lo);
   return l;
 }
 // The header the tile loop reads: the program's, or the lean kernel's copy.
 template <bool kLean>
-__device__ __forceinline__ decltype(auto) tile_header(const HttpHeader& h) {
-  if constexpr (kLean) return make_lean_header(h);
+__device__ __forceinline__ decltype(auto) tile_header(const HttpHeader& h, const Ctx& c) {
+  if constexpr (kLean) return make_lean_header(h, c);
   else return (h);
 }
 // First pass: the request's smallest candidate may be a slow-path rule
@@ -1149,7 +1235,8 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const H& h, const Src
   uint64_t present = 0;
   codes.clear(h.n_dfas);
   // Walk jobs, one loop so that the walk code exists once in the kernel
-  // (instruction-cache footprint): 0 method, 1 path, 2 authority, then the
+  // (instruction-cache footprint; the lean kernel takes jobs 0-2 out of it,
+  // below): 0 method, 1 path, 2 authority, then the
   // values of headers whose name a rule references (first occurrence).  The
   // job index is wave-uniform; for the header jobs each lane first moves its
   // cursor (hj, hp) past headers whose name length no rule uses, so a wave
@@ -1177,7 +1264,30 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const H& h, const Src
   };
   uint32_t dcap = 0;
   const DcapSpec* dspec = reinterpret_cast<const DcapSpec*>(c.img + (kDcap ? h.lds_dcap : 0u));
-  for (uint32_t job = 0;; ++job) {
+  if constexpr (kLean) {
+    // Jobs 0-2 outside the loop: each takes its automaton from the wave's
+    // scalars (LeanHeader::job<J>), so nothing of FieldDesc / DfaDesc is read
+    // or formed per lane and tile.  The loop below runs the header jobs.
+    HPROF(4);
+    if (flags & L7M_HTTP_F_METHOD) {
+      present |= 1u;
+      lean_walk(c, h.template job<0>(), src, pos, mlen, codes, touched, pf_t, prof);
+    }
+    pos += mlen;
+    HPROF(4);
+    if (flags & L7M_HTTP_F_PATH) {
+      present |= 2u;
+      lean_walk(c, h.template job<1>(), src, pos, plen, codes, touched, pf_t, prof);
+    }
+    pos += plen;
+    HPROF(4);
+    if (flags & L7M_HTTP_F_AUTHORITY) {
+      present |= 4u;
+      lean_walk(c, h.template job<2>(), src, pos, alen, codes, touched, pf_t, prof);
+    }
+    pos += alen;
+  }
+  for (uint32_t job = kLean ? 3 : 0;; ++job) {
     HPROF(4);  // (diagnostic build) what followed the previous job's walks
     uint32_t f = kNone, p = pos, len = 0;
     if (job < 3) {
@@ -1219,21 +1329,13 @@ __device__ __forceinline__ int32_t eval_walk(const Ctx& c, const H& h, const Src
     }
     HPROF(2);  // job selection, header-name lookup
     if constexpr (kLean) {
-      // every automaton is walked from LDS and its entries carry the end code
+      // (a header's automata: descriptors per lane, as the generic kernel reads them)
       if (f != kNone) {
         present |= 1ull << f;
-        const FieldDesc& fd = c.fields[f];  // (descriptors per lane, as the generic kernel reads them)
+        const FieldDesc& fd = c.fields[f];
         for (uint32_t k = 0; k < fd.ndfa; ++k) {
           const uint32_t d = fd.dfa_first + k;
-          const DfaDesc& dd = c.dds[d];
-          LdsChain ch;
-          ch.init(dd);
-          if (!dd.start_base) ch.e = 0;  // dead from the start: the dead row (walk_lds skips the walk: the same code, 0)
-          ch.template run<true>(src, p, len, 0);  // (field tails from one word on the LDS stage)
-          const uint32_t code = ch.code_in_entry(c.img, dd.lds_latch, dd.start_latch);
-          HPROF(3);
-          codes.set(d, code);
-          touch(d, code);
+          lean_walk(c, job_dfa(c.dds[d], d, ((h.cand_dfas_lo >> d) & 1u) != 0), src, p, len, codes, touched, pf_t, prof);
         }
       }
     } else if (f != kNone) {
@@ -1628,7 +1730,7 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
   __syncthreads();
 
   const Ctx c = make_ctx(prog, img, h);
-  const auto& th = tile_header<kLean>(h);  // what the tile loop reads of the header
+  const auto& th = tile_header<kLean>(h, c);  // what the tile loop reads of the header
   uint32_t* mycol = col + tid;
   // diagnostic wave timeline per tile (kProf, s_memtime): [0] top wait,
   // [1] walks, [2] entry wait, [3] issue, [4] verify + store, [5] counters;
