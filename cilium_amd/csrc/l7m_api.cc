@@ -72,12 +72,17 @@ int finish_compile(CompileResult&& cr, uint32_t proto, l7m_ruleset** out, char* 
   return L7M_OK;
 }
 
-std::atomic<int> g_resident_cus[64];  // resident workgroups running per device (l7m_batch.cc)
+std::atomic<int> g_resident_cus[kMaxDevices];  // resident workgroups running per device (l7m_batch.cc)
+
+// The current HIP device, or -1 when there is none the library can index.
+int current_device() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices ? dev : -1;
+}
 
 int device_program(l7m_ruleset* rs, const uint32_t** out, int* cus) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
-  if (dev < 0 || dev >= 64) return L7M_EDEVICE;
+  const int dev = current_device();
+  if (dev < 0) return L7M_EDEVICE;
   hipDeviceProp_t prop;
   static thread_local int cached_dev = -1, cached_cus = 0;
   if (cached_dev != dev) {
@@ -134,7 +139,7 @@ struct KafkaCodecDev {
   uint32_t rr = 0;
   std::condition_variable cv;
 };
-KafkaCodecDev g_kcodec[64];
+KafkaCodecDev g_kcodec[kMaxDevices];
 
 // Decode slabs are 2 x maxParseBufSize + 64 KiB (~13 MB) per worker, allocated
 // at the first Kafka launch on a device: 16 workers ~ 211 MB.
@@ -144,11 +149,10 @@ uint32_t codec_workers() {
   return v < 0 ? 0u : v > 4096 ? 4096u : static_cast<uint32_t>(v);
 }
 
-hipError_t launch_kafka_both(const uint32_t* dprog, const KafkaHeader& h, const uint8_t* arena, uint64_t arena_bytes,
-                             const uint64_t* offs, uint64_t n, int32_t* verdicts, unsigned long long* hits,
-                             hipStream_t stream, int cus, uint32_t flags, const uint32_t* ids) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+hipError_t launch_kafka_both(const uint32_t* dprog, const KafkaHeader& h, const BatchRef& b, hipStream_t stream,
+                             int cus, uint32_t flags) {
+  const int dev = current_device();
+  if (dev < 0) return hipErrorInvalidDevice;
   KafkaCodecDev& g = g_kcodec[dev];
   KafkaCodecQueue cq;
   KafkaCodecDev::Slot* slot = nullptr;
@@ -207,14 +211,14 @@ hipError_t launch_kafka_both(const uint32_t* dprog, const KafkaHeader& h, const 
     cq.slabs = g.slabs;
     cq.slab_bytes = g.slab_bytes;
   }
-  hipError_t e = launch_kafka(dprog, h, arena, arena_bytes, offs, n, verdicts, hits, stream, cus, flags, cq, ids);
+  hipError_t e = launch_kafka(dprog, h, b, stream, cus, flags, cq);
   std::lock_guard<std::mutex> lk(g.mu);
-  if (e == hipSuccess && n && !(flags & (L7M_FLAG_DIAG_COPY_ONLY | L7M_FLAG_DIAG_WALK_ONLY)) && cq.cap &&
+  if (e == hipSuccess && b.n && !(flags & (L7M_FLAG_DIAG_COPY_ONLY | L7M_FLAG_DIAG_WALK_ONLY)) && cq.cap &&
       cq.workers) {
     e = hipStreamWaitEvent(stream, g.p2_done, 0);
-    if (e == hipSuccess) e = launch_kafka_codec(dprog, arena, arena_bytes, offs, n, verdicts, hits, stream, cq);
+    if (e == hipSuccess) e = launch_kafka_codec(dprog, b, stream, cq);
     if (e == hipSuccess) e = hipEventRecord(g.p2_done, stream);
-  } else if (e == hipSuccess && n) {
+  } else if (e == hipSuccess && b.n) {
     e = hipMemsetAsync(slot->qhdr, 0, 16, stream);  // no second pass to reset the queue header
   }
   const hipError_t e2 = hipEventRecord(slot->done, stream);
@@ -224,8 +228,21 @@ hipError_t launch_kafka_both(const uint32_t* dprog, const KafkaHeader& h, const 
   return e;
 }
 
-int launch(const l7m_ruleset* crs, const void* arena, size_t arena_bytes, const void* offs, size_t n, void* verdicts,
-           void* hits, hipStream_t stream, uint32_t flags, const void* ids = nullptr,
+// The one place a BatchRef is built: the ABI's untyped addresses, cast once.
+BatchRef batch_ref(const void* arena, size_t arena_bytes, const void* offs, size_t n, void* verdicts, void* hits,
+                   const void* ids = nullptr) {
+  return BatchRef{static_cast<const uint8_t*>(arena), arena_bytes, static_cast<const uint64_t*>(offs), n,
+                  static_cast<int32_t*>(verdicts), static_cast<unsigned long long*>(hits),
+                  static_cast<const uint32_t*>(ids)};
+}
+
+// ... and the read-only view of a decided batch, for the side-effect launchers.
+BatchView batch_view(const void* arena, size_t arena_bytes, const void* offs, size_t n, const void* verdicts) {
+  return BatchView{static_cast<const uint8_t*>(arena), arena_bytes, static_cast<const uint64_t*>(offs), n,
+                   static_cast<const int32_t*>(verdicts)};
+}
+
+int launch(const l7m_ruleset* crs, const BatchRef& b, hipStream_t stream, uint32_t flags,
            const DoneSignal* done = nullptr, bool* signalled = nullptr) {
   if (signalled) *signalled = false;
   auto* rs = const_cast<l7m_ruleset*>(crs);
@@ -236,14 +253,13 @@ int launch(const l7m_ruleset* crs, const void* arena, size_t arena_bytes, const 
   {
     // resident batcher workgroups each hold a CU: a persistent grid sized to
     // every CU would leave its last workgroup waiting for another to finish
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int busy = dev >= 0 && dev < 64 ? g_resident_cus[dev].load(std::memory_order_relaxed) : 0;
+    const int dev = current_device();
+    const int busy = dev >= 0 ? g_resident_cus[dev].load(std::memory_order_relaxed) : 0;
     if (busy > 0) cus = cus - busy > 1 ? cus - busy : 1;
   }
   hipError_t e;
   if (rs->proto == L7M_PROTO_HTTP) {
-    if (ids) return L7M_EINVAL;  // HTTP records carry their remote identity
+    if (b.ids) return L7M_EINVAL;  // HTTP records carry their remote identity
     HttpHeader h;
     std::memcpy(&h, rs->program.data(), sizeof h);
     if (http_stage_bytes(h) == 0) return L7M_ETOOBIG;
@@ -254,17 +270,12 @@ int launch(const l7m_ruleset* crs, const void* arena, size_t arena_bytes, const 
       if (dd[k].lit_tab != kNone) flags |= kLaunchLiterals;
     if (rs->info.n_dense_dfas) flags |= kLaunchDense;  // (value and forced-capture R automata)
     if (rs->http_lean) flags |= kLaunchLean;
-    e = launch_http(dprog, h, static_cast<const uint8_t*>(arena), arena_bytes, static_cast<const uint64_t*>(offs),
-                    n, static_cast<int32_t*>(verdicts), static_cast<unsigned long long*>(hits),
-                    stream, cus, flags, done);
-    if (signalled) *signalled = done && n && !h.n_slow && e == hipSuccess;
+    e = launch_http(dprog, h, b, stream, cus, flags, done);
+    if (signalled) *signalled = done && b.n && !h.n_slow && e == hipSuccess;
   } else if (rs->proto == L7M_PROTO_KAFKA) {
     KafkaHeader h;
     std::memcpy(&h, rs->program.data(), sizeof h);
-    e = launch_kafka_both(dprog, h, static_cast<const uint8_t*>(arena), arena_bytes,
-                          static_cast<const uint64_t*>(offs), n, static_cast<int32_t*>(verdicts),
-                          static_cast<unsigned long long*>(hits), stream, cus, flags,
-                          static_cast<const uint32_t*>(ids));
+    e = launch_kafka_both(dprog, h, b, stream, cus, flags);
   } else {
     return L7M_EINVAL;
   }
@@ -276,8 +287,6 @@ int launch(const l7m_ruleset* crs, const void* arena, size_t arena_bytes, const 
 // l7m_eval is reentrant: each concurrent call takes its own context (stream +
 // device buffers grown to the largest batch seen) from a per-device free
 // list, so steady-state calls allocate nothing and never share buffers.
-constexpr int kMaxDevices = 64;
-
 struct EvalCtx {
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;  // second stream of the chunked pipeline (lazily created)
@@ -385,19 +394,22 @@ const void* mapped_host_range(const void* p, size_t bytes) {
   return a.devicePointer;
 }
 
-int eval_pipelined(EvalCtx* c, const l7m_ruleset* rs, const uint8_t* arena, size_t arena_bytes,
-                   const uint64_t* offsets, size_t n, const uint32_t* ids, int32_t* verdicts, bool hits,
-                   size_t abytes, size_t nctr, uint32_t flags) {
+// host: the caller's batch in host memory; its hits say only whether to count
+// (c->hhost receives the counters).
+int eval_pipelined(EvalCtx* c, const l7m_ruleset* rs, const BatchRef& host, size_t abytes, size_t nctr,
+                   uint32_t flags) {
   if (!c->stream2 && hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess) return L7M_EDEVICE;
   if (!c->ev && hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) != hipSuccess) return L7M_EDEVICE;
   if (!c->ev2 && hipEventCreateWithFlags(&c->ev2, hipEventDisableTiming) != hipSuccess) return L7M_EDEVICE;
   const hipStream_t s0 = c->stream, s1 = c->stream2;
+  const uint64_t* offsets = host.offs;
+  const size_t n = host.n, arena_bytes = host.arena_bytes;
   auto* da = static_cast<uint8_t*>(c->arena);
   auto* doffs = static_cast<uint64_t*>(c->offs);
   auto* dverd = static_cast<int32_t*>(c->verd);
   auto* dids = static_cast<uint32_t*>(c->ids);
   bool ok = hipMemsetAsync(da + arena_bytes, 0, abytes - arena_bytes, s0) == hipSuccess &&
-            (!hits || hipMemsetAsync(c->hits, 0, nctr * 8, s0) == hipSuccess) &&
+            (!host.hits || hipMemsetAsync(c->hits, 0, nctr * 8, s0) == hipSuccess) &&
             hipEventRecord(c->ev, s0) == hipSuccess && hipStreamWaitEvent(s1, c->ev, 0) == hipSuccess;
   int rc = ok ? L7M_OK : L7M_EDEVICE;
   size_t lo = 0;
@@ -408,21 +420,23 @@ int eval_pipelined(EvalCtx* c, const l7m_ruleset* rs, const uint8_t* arena, size
     if (hi == lo) hi = lo + 1;
     const uint64_t b = hi < n ? offsets[hi] : arena_bytes;
     const hipStream_t st = (k & 1) ? s1 : s0;
-    ok = hipMemcpyAsync(da + a, arena + a, b - a, hipMemcpyHostToDevice, st) == hipSuccess &&
+    ok = hipMemcpyAsync(da + a, host.arena + a, b - a, hipMemcpyHostToDevice, st) == hipSuccess &&
          hipMemcpyAsync(doffs + lo, offsets + lo, (hi - lo) * 8, hipMemcpyHostToDevice, st) == hipSuccess &&
-         (!ids || hipMemcpyAsync(dids + lo, ids + lo, (hi - lo) * 4, hipMemcpyHostToDevice, st) == hipSuccess);
+         (!host.ids ||
+          hipMemcpyAsync(dids + lo, host.ids + lo, (hi - lo) * 4, hipMemcpyHostToDevice, st) == hipSuccess);
     if (!ok) rc = L7M_EDEVICE;
     if (rc == L7M_OK)
-      rc = launch(rs, da, arena_bytes, doffs + lo, hi - lo, dverd + lo, hits ? c->hits : nullptr, st, flags,
-                  ids ? dids + lo : nullptr);
+      rc = launch(rs, batch_ref(da, arena_bytes, doffs + lo, hi - lo, dverd + lo, host.hits ? c->hits : nullptr,
+                                host.ids ? dids + lo : nullptr),
+                  st, flags);
     if (rc == L7M_OK &&
-        hipMemcpyAsync(verdicts + lo, dverd + lo, (hi - lo) * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+        hipMemcpyAsync(host.verdicts + lo, dverd + lo, (hi - lo) * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
       rc = L7M_EDEVICE;
     lo = hi;
   }
   // join: stream 0 waits for stream 1, then the counters come back
   if (hipEventRecord(c->ev2, s1) != hipSuccess || hipStreamWaitEvent(s0, c->ev2, 0) != hipSuccess) rc = L7M_EDEVICE;
-  if (rc == L7M_OK && hits &&
+  if (rc == L7M_OK && host.hits &&
       hipMemcpyAsync(c->hhost.data(), c->hits, nctr * 8, hipMemcpyDeviceToHost, s0) != hipSuccess)
     rc = L7M_EDEVICE;
   if (hipStreamSynchronize(s0) != hipSuccess && rc == L7M_OK) rc = L7M_EDEVICE;
@@ -438,7 +452,7 @@ namespace l7m {
 // be served by kafka_resident_kernel, with its device program, instantiation,
 // record stage and serial.
 void resident_running(int dev, int delta) {
-  if (dev >= 0 && dev < 64) g_resident_cus[dev].fetch_add(delta, std::memory_order_relaxed);
+  if (dev >= 0 && dev < kMaxDevices) g_resident_cus[dev].fetch_add(delta, std::memory_order_relaxed);
 }
 
 bool resident_program(l7m_ruleset* rs, const uint32_t** dprog, int* kind, uint32_t* stage, uint64_t* serial) {
@@ -463,8 +477,9 @@ int eval_device_signal(const l7m_ruleset* rs, const void* d_arena, size_t arena_
   *signalled = false;
   if (!rs || (n && (!d_arena || !d_offs || !d_verdicts))) return L7M_EINVAL;
   if (reinterpret_cast<uintptr_t>(d_arena) & 15) return L7M_EINVAL;
-  if (rs->proto != L7M_PROTO_HTTP) return launch(rs, d_arena, arena_bytes, d_offs, n, d_verdicts, nullptr, stream, 0);
-  return launch(rs, d_arena, arena_bytes, d_offs, n, d_verdicts, nullptr, stream, 0, nullptr, &sig, signalled);
+  const BatchRef b = batch_ref(d_arena, arena_bytes, d_offs, n, d_verdicts, nullptr);
+  if (rs->proto != L7M_PROTO_HTTP) return launch(rs, b, stream, 0);
+  return launch(rs, b, stream, 0, &sig, signalled);
 }
 
 }  // namespace l7m
@@ -545,7 +560,7 @@ void l7m_retain(l7m_ruleset* rs) {
 void l7m_release(l7m_ruleset* rs) {
   if (!rs) return;
   if (rs->refs.fetch_sub(1) != 1) return;
-  for (int d = 0; d < 64; ++d)
+  for (int d = 0; d < kMaxDevices; ++d)
     if (rs->dprog[d]) {
       int cur = 0;
       (void)hipGetDevice(&cur);
@@ -784,10 +799,9 @@ int l7m_http_access_log_device(const void* d_arena, size_t arena_bytes, const vo
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
   const hipError_t e = launch_http_log(
-      static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets), n,
-      static_cast<const int32_t*>(d_verdicts), c, select ? select : (L7M_LOG_FORWARDED | L7M_LOG_DENIED),
-      static_cast<uint8_t*>(d_out), cap, static_cast<uint64_t*>(d_entry_offs), static_cast<uint64_t*>(d_total),
-      static_cast<hipStream_t>(hip_stream));
+      batch_view(d_arena, arena_bytes, d_rec_offsets, n, d_verdicts), c,
+      select ? select : (L7M_LOG_FORWARDED | L7M_LOG_DENIED), static_cast<uint8_t*>(d_out), cap,
+      static_cast<uint64_t*>(d_entry_offs), static_cast<uint64_t*>(d_total), static_cast<hipStream_t>(hip_stream));
   return status_of(e);
 }
 
@@ -800,8 +814,7 @@ int l7m_kafka_deny_responses_device(const void* d_arena, size_t arena_bytes, con
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
   const hipError_t e = launch_kafka_side(
-      false, static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets), n,
-      static_cast<const int32_t*>(d_verdicts), 0, static_cast<uint8_t*>(d_out), cap,
+      false, batch_view(d_arena, arena_bytes, d_rec_offsets, n, d_verdicts), 0, static_cast<uint8_t*>(d_out), cap,
       static_cast<uint64_t*>(d_resp_offs), static_cast<uint64_t*>(d_total), static_cast<hipStream_t>(hip_stream));
   return status_of(e);
 }
@@ -816,8 +829,7 @@ int l7m_kafka_access_log_device(const void* d_arena, size_t arena_bytes, const v
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
   const hipError_t e = launch_kafka_side(
-      true, static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets), n,
-      static_cast<const int32_t*>(d_verdicts), select, static_cast<uint8_t*>(d_out), cap,
+      true, batch_view(d_arena, arena_bytes, d_rec_offsets, n, d_verdicts), select, static_cast<uint8_t*>(d_out), cap,
       static_cast<uint64_t*>(d_first), static_cast<uint64_t*>(d_total), static_cast<hipStream_t>(hip_stream));
   return status_of(e);
 }
@@ -831,10 +843,9 @@ int l7m_proxy_stats_update_device(l7m_proxy_stats_table* t, uint32_t proto, cons
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return L7M_EDEVICE;
   std::vector<uint64_t> counters(kStatsCounters);
-  const hipError_t e = launch_http_stats(
-      static_cast<const uint8_t*>(d_arena), arena_bytes, static_cast<const uint64_t*>(d_rec_offsets),
-      static_cast<const int32_t*>(d_verdicts), n, (ingress ? 65536u : 0u) | port, counters.data(),
-      static_cast<hipStream_t>(hip_stream));
+  const hipError_t e =
+      launch_http_stats(batch_view(d_arena, arena_bytes, d_rec_offsets, n, d_verdicts), (ingress ? 65536u : 0u) | port,
+                        counters.data(), static_cast<hipStream_t>(hip_stream));
   if (e != hipSuccess) return status_of(e);
   proxy_stats_merge_http(t, counters.data());
   return L7M_OK;
@@ -846,8 +857,8 @@ int l7m_eval_device(const l7m_ruleset* rs, const void* d_arena, size_t arena_byt
   if (!rs || (n && (!d_arena || !d_offsets || !d_verdicts))) return L7M_EINVAL;
   // The kernels stream records with aligned 16-byte loads.
   if (reinterpret_cast<uintptr_t>(d_arena) & 15) return L7M_EINVAL;
-  return launch(rs, d_arena, arena_bytes, d_offsets, n, d_verdicts, d_hits, static_cast<hipStream_t>(hip_stream),
-                flags);
+  return launch(rs, batch_ref(d_arena, arena_bytes, d_offsets, n, d_verdicts, d_hits),
+                static_cast<hipStream_t>(hip_stream), flags);
 }
 
 int l7m_eval_device_ids(const l7m_ruleset* rs, const void* d_arena, size_t arena_bytes, const void* d_offsets,
@@ -856,8 +867,8 @@ int l7m_eval_device_ids(const l7m_ruleset* rs, const void* d_arena, size_t arena
   if (!rs || (n && (!d_arena || !d_offsets || !d_verdicts))) return L7M_EINVAL;
   if (reinterpret_cast<uintptr_t>(d_arena) & 15) return L7M_EINVAL;
   if (rs->proto != L7M_PROTO_KAFKA) return L7M_EINVAL;
-  return launch(rs, d_arena, arena_bytes, d_offsets, n, d_verdicts, d_hits, static_cast<hipStream_t>(hip_stream),
-                flags, d_ids);
+  return launch(rs, batch_ref(d_arena, arena_bytes, d_offsets, n, d_verdicts, d_hits, d_ids),
+                static_cast<hipStream_t>(hip_stream), flags);
 }
 
 int l7m_eval(const l7m_ruleset* rs, const uint8_t* arena, size_t arena_bytes,
@@ -872,8 +883,8 @@ int l7m_eval_ids(const l7m_ruleset* rs, const uint8_t* arena, size_t arena_bytes
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return L7M_EDEVICE;
   if (n == 0) return L7M_OK;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return L7M_EDEVICE;
+  const int dev = current_device();
+  if (dev < 0) return L7M_EDEVICE;
   const size_t nctr = rs->info.n_counters;
   // Pad the arena copy so that the kernels' aligned word loads never run past it.
   const size_t abytes = (arena_bytes + 64) & ~size_t(3);
@@ -883,47 +894,33 @@ int l7m_eval_ids(const l7m_ruleset* rs, const uint8_t* arena, size_t arena_bytes
   // kernels' aligned over-reads stay inside [arena, arena + abytes))
   const void* za = (reinterpret_cast<uintptr_t>(arena) & 15) ? nullptr : mapped_host_range(arena, abytes);
   int rc = c->reserve(za ? 0 : abytes, n, nctr, ids != nullptr);
-  if (rc == L7M_OK && za) {
+  if (rc == L7M_OK && !za && arena_bytes >= 2 * kPipeChunkBytes && ascending(offsets, n, arena_bytes)) {
+    rc = eval_pipelined(c, rs, batch_ref(arena, arena_bytes, offsets, n, verdicts, hits, ids), abytes, nctr, flags);
+  } else if (rc == L7M_OK) {
     const hipStream_t st = c->stream;
-    const void* zo = (reinterpret_cast<uintptr_t>(offsets) & 7) ? nullptr : mapped_host_range(offsets, n * 8);
-    const void* zi = ids && !(reinterpret_cast<uintptr_t>(ids) & 3) ? mapped_host_range(ids, n * 4) : nullptr;
-    bool ok = (zo || hipMemcpyAsync(c->offs, offsets, n * 8, hipMemcpyHostToDevice, st) == hipSuccess) &&
+    // each source is its zero-copy device address (only beside a zero-copy
+    // arena), or the context's buffer after a copy
+    const void* zo = za && !(reinterpret_cast<uintptr_t>(offsets) & 7) ? mapped_host_range(offsets, n * 8) : nullptr;
+    const void* zi = za && ids && !(reinterpret_cast<uintptr_t>(ids) & 3) ? mapped_host_range(ids, n * 4) : nullptr;
+    bool ok = (za || (hipMemsetAsync(static_cast<uint8_t*>(c->arena) + arena_bytes, 0, abytes - arena_bytes, st) ==
+                          hipSuccess &&
+                      hipMemcpyAsync(c->arena, arena, arena_bytes, hipMemcpyHostToDevice, st) == hipSuccess)) &&
+              (zo || hipMemcpyAsync(c->offs, offsets, n * 8, hipMemcpyHostToDevice, st) == hipSuccess) &&
               (!ids || zi || hipMemcpyAsync(c->ids, ids, n * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
               (!hits || hipMemsetAsync(c->hits, 0, nctr * 8, st) == hipSuccess);
     if (!ok) rc = L7M_EDEVICE;
     if (rc == L7M_OK)
-      rc = launch(rs, za, arena_bytes, zo ? zo : c->offs, n, c->verd, hits ? c->hits : nullptr, st, flags,
-                  ids ? (zi ? zi : c->ids) : nullptr);
+      rc = launch(rs, batch_ref(za ? za : c->arena, arena_bytes, zo ? zo : c->offs, n, c->verd,
+                                hits ? c->hits : nullptr, ids ? (zi ? zi : c->ids) : nullptr),
+                  st, flags);
     if (rc == L7M_OK && hipMemcpyAsync(verdicts, c->verd, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
       rc = L7M_EDEVICE;
     if (rc == L7M_OK && hits && hipMemcpyAsync(c->hhost.data(), c->hits, nctr * 8, hipMemcpyDeviceToHost, st) != hipSuccess)
       rc = L7M_EDEVICE;
     if (hipStreamSynchronize(st) != hipSuccess && rc == L7M_OK) rc = L7M_EDEVICE;
-    if (rc == L7M_OK && hits)
-      for (size_t i = 0; i < nctr; ++i) hits[i] += c->hhost[i];
-  } else if (rc == L7M_OK && arena_bytes >= 2 * kPipeChunkBytes && ascending(offsets, n, arena_bytes)) {
-    rc = eval_pipelined(c, rs, arena, arena_bytes, offsets, n, ids, verdicts, hits != nullptr, abytes, nctr, flags);
-    if (rc == L7M_OK && hits)
-      for (size_t i = 0; i < nctr; ++i) hits[i] += c->hhost[i];
-  } else if (rc == L7M_OK) {
-    const hipStream_t st = c->stream;
-    bool ok = hipMemsetAsync(static_cast<uint8_t*>(c->arena) + arena_bytes, 0, abytes - arena_bytes, st) == hipSuccess &&
-              hipMemcpyAsync(c->arena, arena, arena_bytes, hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(c->offs, offsets, n * 8, hipMemcpyHostToDevice, st) == hipSuccess &&
-              (!ids || hipMemcpyAsync(c->ids, ids, n * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
-              (!hits || hipMemsetAsync(c->hits, 0, nctr * 8, st) == hipSuccess);
-    if (!ok) rc = L7M_EDEVICE;
-    if (rc == L7M_OK)
-      rc = launch(rs, c->arena, arena_bytes, c->offs, n, c->verd, hits ? c->hits : nullptr, st, flags,
-                  ids ? c->ids : nullptr);
-    if (rc == L7M_OK && hipMemcpyAsync(verdicts, c->verd, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
-      rc = L7M_EDEVICE;
-    if (rc == L7M_OK && hits && hipMemcpyAsync(c->hhost.data(), c->hits, nctr * 8, hipMemcpyDeviceToHost, st) != hipSuccess)
-      rc = L7M_EDEVICE;
-    if (hipStreamSynchronize(st) != hipSuccess && rc == L7M_OK) rc = L7M_EDEVICE;
-    if (rc == L7M_OK && hits)
-      for (size_t i = 0; i < nctr; ++i) hits[i] += c->hhost[i];
   }
+  if (rc == L7M_OK && hits)
+    for (size_t i = 0; i < nctr; ++i) hits[i] += c->hhost[i];
   release_ctx(dev, c);
   return rc;
 }

@@ -108,10 +108,71 @@ struct DoneSignal {
   uint32_t* flag;
   uint32_t seq;
 };
-hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t* arena,
-                       uint64_t arena_bytes, const uint64_t* offs, uint64_t n, int32_t* verdicts,
-                       unsigned long long* hits, hipStream_t stream, int num_cus, uint32_t flags,
-                       const DoneSignal* done = nullptr);
+// One batch as the verdict kernels see it: n records at offs[0..n) of the
+// arena (device-visible addresses), one verdict each, the rule counters
+// (nullptr: not counted) and the Kafka requests' source identities (nullptr:
+// none).  Built once where a batch enters the launch path (l7m_api.cc
+// batch_ref); every launcher below that only reads it.
+struct BatchRef {
+  const uint8_t* arena;
+  uint64_t arena_bytes;
+  const uint64_t* offs;
+  uint64_t n;
+  int32_t* verdicts;
+  unsigned long long* hits;
+  const uint32_t* ids;
+};
+// A decided batch, read-only: what the side-effect launchers (access log,
+// proxy statistics, Kafka deny responses and log records) take.
+struct BatchView {
+  const uint8_t* arena;
+  uint64_t arena_bytes;
+  const uint64_t* offs;
+  uint64_t n;
+  const int32_t* verdicts;
+};
+// What a family's launcher (launch_http, launch_kafka) decides before it
+// picks an instantiation: the first pass's grid, its dynamic LDS, the record
+// stage per wave, the stream and the device program.  The per-instantiation
+// launchers (launch_one, launch_slow, launch_k) only read it; launch_slow reads
+// the stream and the program alone (the slow pass has its own grid and LDS).
+struct LaunchPlan {
+  dim3 grid;
+  size_t lds;
+  uint32_t stage;
+  hipStream_t stream;
+  const uint32_t* dprog;
+};
+// Persistent grid of a verdict kernel: per_cu workgroups of `block` threads
+// per CU; fewer for small batches (>= 2 records per lane, two tiles per wave).
+inline dim3 batch_grid(uint64_t n, int num_cus, uint32_t block, uint32_t per_cu = 1) {
+  const uint64_t blocks = static_cast<uint64_t>(num_cus > 0 ? num_cus : 256) * per_cu;
+  const uint64_t want = (n + 2 * block - 1) / (2 * block);
+  return dim3(static_cast<uint32_t>(want < blocks ? want : blocks));
+}
+hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const BatchRef& b, hipStream_t stream, int num_cus,
+                       uint32_t flags, const DoneSignal* done = nullptr);
+// The slow pass of launch_http (programs with kCrSlow rules): the two tiers'
+// queues (count + up to n indices), executor scratch, workgroups and work
+// counters ([0] tier 1, [64] tier 2), in one stream-ordered allocation.
+struct HttpSlowPass {
+  uint32_t* slowq = nullptr;
+  uint32_t* slowq2 = nullptr;
+  uint32_t* vms[2] = {nullptr, nullptr};
+  uint32_t* work = nullptr;
+  uint32_t blocks[2] = {0, 0};
+};
+// First-pass / slow-pass launches of the ECMAScript instantiations of feature
+// set F (l7m_http_impl.h kFeat*): defined and explicitly instantiated in
+// l7m_http_feat.hip, one translation unit per F < 4 holding F and F + 4.
+// The definitions are deliberately not in a header: a use of any F in 0..7
+// links against those four objects.
+template <int F>
+hipError_t launch_http_main(const LaunchPlan& p, const BatchRef& b, int mode, int R, bool lean, uint32_t* slowq,
+                            DoneSignal done);
+template <int F>
+hipError_t launch_http_slow(const LaunchPlan& p, const HttpHeader& h, const BatchRef& b, const HttpSlowPass& s, int R,
+                            int tier);
 
 // HTTP/1.x request heads -> request arena (l7m_http_wire.hip): measure pass,
 // scan and emit pass enqueued on `stream` by l7m_tile_scan.h's tile_pipeline,
@@ -126,24 +187,20 @@ hipError_t launch_http_wire(const uint8_t* wire, uint64_t wire_bytes, const uint
 // scan and emit pass enqueued on `stream`.  entry_offs (u64[n + 1]) and *total
 // are always written; nothing of `out` is when the total exceeds cap.
 struct LogConstsFixed;
-hipError_t launch_http_log(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n,
-                           const int32_t* verdicts, const LogConstsFixed& c, uint32_t select, uint8_t* out,
-                           uint64_t cap, uint64_t* entry_offs, uint64_t* total, hipStream_t stream);
+hipError_t launch_http_log(const BatchView& b, const LogConstsFixed& c, uint32_t select, uint8_t* out, uint64_t cap,
+                           uint64_t* entry_offs, uint64_t* total, hipStream_t stream);
 // Request counters of a decided HTTP batch per (direction, port, verdict
 // class) into host_counters (l7m_http_log.h kStatsCounters words; caller_row =
 // ingress * 65536 + port for records that do not validate).  Synchronises
 // `stream`.
-hipError_t launch_http_stats(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs,
-                             const int32_t* verdicts, uint64_t n, uint32_t caller_row, uint64_t* host_counters,
-                             hipStream_t stream);
+hipError_t launch_http_stats(const BatchView& b, uint32_t caller_row, uint64_t* host_counters, hipStream_t stream);
 
 // Deny responses (log = false: sizes and cap in bytes, `select` unused) or
 // per-topic log records (log = true: in records) of a decided Kafka batch
 // (l7m_kafka_side.hip): measure pass, scan and emit pass enqueued on `stream`.
 // out_offs (u64[n + 1]) and *total are always written; nothing of `out` is
 // when the total exceeds cap.
-hipError_t launch_kafka_side(bool log, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n,
-                             const int32_t* verdicts, uint32_t select, uint8_t* out, uint64_t cap,
+hipError_t launch_kafka_side(bool log, const BatchView& b, uint32_t select, uint8_t* out, uint64_t cap,
                              uint64_t* out_offs, uint64_t* total, hipStream_t stream);
 
 // Connection byte streams -> head slices for the wire decoder, or Kafka
@@ -228,12 +285,8 @@ struct KafkaCodecQueue {
   uint64_t slab_bytes = 0;
 };
 
-hipError_t launch_kafka(const uint32_t* dprog, const KafkaHeader& h, const uint8_t* arena,
-                        uint64_t arena_bytes, const uint64_t* offs, uint64_t n, int32_t* verdicts,
-                        unsigned long long* hits, hipStream_t stream, int num_cus, uint32_t flags,
-                        const KafkaCodecQueue& cq, const uint32_t* ids);
-hipError_t launch_kafka_codec(const uint32_t* dprog, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs,
-                              uint64_t n, int32_t* verdicts, unsigned long long* hits, hipStream_t stream,
-                              const KafkaCodecQueue& cq);
+hipError_t launch_kafka(const uint32_t* dprog, const KafkaHeader& h, const BatchRef& b, hipStream_t stream,
+                        int num_cus, uint32_t flags, const KafkaCodecQueue& cq);
+hipError_t launch_kafka_codec(const uint32_t* dprog, const BatchRef& b, hipStream_t stream, const KafkaCodecQueue& cq);
 
 }  // namespace l7m

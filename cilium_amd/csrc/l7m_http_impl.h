@@ -2058,32 +2058,28 @@ __global__ __launch_bounds__(kSlowBlock) void http_slow_kernel(const uint32_t* _
 
 
 template <int kHits, int kReg, int kAblate = 0, int kFeat = 0>
-hipError_t launch_one(dim3 grid, size_t lds, hipStream_t stream, const uint32_t* dprog, const uint8_t* arena,
-                       uint64_t arena_bytes, const uint64_t* offs, uint64_t n, int32_t* verdicts,
-                       unsigned long long* hits, uint32_t stage, uint32_t* scratch = nullptr,
-                       uint32_t* slowq = nullptr, DoneSignal done = DoneSignal{nullptr, nullptr, 0}) {
+hipError_t launch_one(const LaunchPlan& p, const BatchRef& b, uint32_t* scratch = nullptr, uint32_t* slowq = nullptr,
+                      DoneSignal done = DoneSignal{nullptr, nullptr, 0}) {
   // allow > 64 KiB of dynamic LDS (gfx950: 160 KiB per CU); set per device
   // and instantiation, thread-safely (l7m_device.h)
   const hipError_t e = set_lds_attr_once(reinterpret_cast<const void*>(http_eval_kernel<kHits, kReg, kAblate, kFeat>),
                                          kHttpLdsBytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((http_eval_kernel<kHits, kReg, kAblate, kFeat>), grid, dim3(kBlock), lds, stream, dprog, arena, arena_bytes,
-                     offs, n, verdicts, hits, stage, scratch, slowq, done);
+  hipLaunchKernelGGL((http_eval_kernel<kHits, kReg, kAblate, kFeat>), p.grid, dim3(kBlock), p.lds, p.stream, p.dprog,
+                     b.arena, b.arena_bytes, b.offs, b.n, b.verdicts, b.hits, p.stage, scratch, slowq, done);
   return hipGetLastError();
 }
 
 template <int kReg, int kFeat, int kTier>
-hipError_t launch_slow(const HttpHeader& h, uint32_t blocks, hipStream_t stream, const uint32_t* dprog,
-                              const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n,
-                              int32_t* verdicts, unsigned long long* hits, const uint32_t* slowq, uint32_t* slowq2,
-                              uint32_t* vmscratch, uint32_t* work) {
+hipError_t launch_slow(const LaunchPlan& p, const HttpHeader& h, const BatchRef& b, const HttpSlowPass& s) {
   const size_t lds = http_slow_lds_bytes(h, kReg != 0);
   if (lds > kHttpLdsBytes) return hipErrorInvalidValue;
   const hipError_t e =
       set_lds_attr_once(reinterpret_cast<const void*>(http_slow_kernel<kReg, kFeat, kTier>), kHttpLdsBytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((http_slow_kernel<kReg, kFeat, kTier>), dim3(blocks), dim3(kSlowBlock), lds, stream, dprog, arena,
-                     arena_bytes, offs, n, verdicts, hits, slowq, slowq2, vmscratch, work);
+  hipLaunchKernelGGL((http_slow_kernel<kReg, kFeat, kTier>), dim3(s.blocks[kTier - 1]), dim3(kSlowBlock), lds, p.stream,
+                     p.dprog, b.arena, b.arena_bytes, b.offs, b.n, b.verdicts, b.hits, s.slowq, s.slowq2,
+                     s.vms[kTier - 1], s.work + (kTier - 1) * 64);
   return hipGetLastError();
 }
 

@@ -225,10 +225,9 @@ __global__ __launch_bounds__(kTileThreads) void http_stats_count(const uint8_t* 
 
 }  // namespace
 
-hipError_t launch_http_log(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n,
-                           const int32_t* verdicts, const LogConstsFixed& c, uint32_t select, uint8_t* out,
-                           uint64_t cap, uint64_t* entry_offs, uint64_t* total, hipStream_t stream) {
-  if (n == 0) {
+hipError_t launch_http_log(const BatchView& b, const LogConstsFixed& c, uint32_t select, uint8_t* out, uint64_t cap,
+                           uint64_t* entry_offs, uint64_t* total, hipStream_t stream) {
+  if (b.n == 0) {
     hipError_t e = hipMemsetAsync(total, 0, sizeof(uint64_t), stream);
     if (e == hipSuccess && entry_offs) e = hipMemsetAsync(entry_offs, 0, sizeof(uint64_t), stream);
     return e;
@@ -236,21 +235,19 @@ hipError_t launch_http_log(const uint8_t* arena, uint64_t arena_bytes, const uin
   const hipError_t e = set_lds_attr_once(reinterpret_cast<const void*>(&http_log_emit), kLogLds);
   if (e != hipSuccess) return e;
   return tile_pipeline(
-      n, {total}, 0, stream,
+      b.n, {total}, 0, stream,
       [&](uint32_t tiles, uint64_t* tile_sums, void*) {
-        http_log_measure<<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(arena, arena_bytes, offs, n, verdicts, c,
-                                                                         select, entry_offs, tile_sums);
+        http_log_measure<<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(b.arena, b.arena_bytes, b.offs, b.n,
+                                                                         b.verdicts, c, select, entry_offs, tile_sums);
       },
       [&](uint32_t tiles, const uint64_t* tile_base, void*) {
         http_log_emit<<<dim3(tiles), dim3(kTileThreads), kLogLds, stream>>>(
-            arena, arena_bytes, offs, n, verdicts, c, out, cap, entry_offs, tile_base, total);
+            b.arena, b.arena_bytes, b.offs, b.n, b.verdicts, c, out, cap, entry_offs, tile_base, total);
       });
 }
 
-hipError_t launch_http_stats(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs,
-                             const int32_t* verdicts, uint64_t n, uint32_t caller_row, uint64_t* host_counters,
-                             hipStream_t stream) {
-  const uint64_t groups = (n + kStatsSpan * kTileThreads - 1) / (kStatsSpan * kTileThreads);
+hipError_t launch_http_stats(const BatchView& b, uint32_t caller_row, uint64_t* host_counters, hipStream_t stream) {
+  const uint64_t groups = (b.n + kStatsSpan * kTileThreads - 1) / (kStatsSpan * kTileThreads);
   if (groups > 0x7fffffffull) return hipErrorInvalidValue;
   const size_t bytes = static_cast<size_t>(kStatsCounters) * sizeof(uint64_t);
   void* scratch = nullptr;  // one kernel, no sizes or scan: not a tile_pipeline, so the scratch is handled here
@@ -259,7 +256,7 @@ hipError_t launch_http_stats(const uint8_t* arena, uint64_t arena_bytes, const u
   e = hipMemsetAsync(scratch, 0, bytes, stream);
   if (e == hipSuccess && groups) {
     http_stats_count<<<dim3(static_cast<uint32_t>(groups)), dim3(kTileThreads), 0, stream>>>(
-        arena, arena_bytes, offs, verdicts, n, caller_row, static_cast<unsigned long long*>(scratch));
+        b.arena, b.arena_bytes, b.offs, b.verdicts, b.n, caller_row, static_cast<unsigned long long*>(scratch));
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(host_counters, scratch, bytes, hipMemcpyDeviceToHost, stream);

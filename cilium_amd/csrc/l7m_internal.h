@@ -26,6 +26,8 @@ inline uint32_t name_hash(const std::string& s) {
   return name_hash_final(h, static_cast<uint32_t>(s.size()));
 }
 
+constexpr int kMaxDevices = 64;  // HIP devices the library can index: every per-device array and check
+
 constexpr uint32_t kDefaultLdsBudget = 48u * 1024u;  // bytes of DFA tables in the LDS image
 constexpr uint32_t kLdsCtBudget = 24u * 1024u;       // ... including candidate tables
 
@@ -102,5 +104,5 @@ struct l7m_ruleset {
   std::vector<l7m_rule_origin> origin;  // HTTP verdict index -> NPDS position
   bool http_lean = false;               // HTTP: launched with kLaunchLean (l7m_dispatch.h http_program_lean)
   std::mutex mu;
-  void* dprog[64] = {nullptr};  // per HIP device
+  void* dprog[l7m::kMaxDevices] = {nullptr};  // per HIP device
 };

@@ -916,36 +916,46 @@ __global__ __launch_bounds__(kKBlock) void kafka_resident_kernel(ResidentBox* bo
 }
 
 template <int kHits, int kAblate = 0, bool kCliLds = false, bool kGroups = false>
-static hipError_t launch_k(dim3 grid, size_t lds, hipStream_t stream, const uint32_t* dprog, const uint8_t* arena,
-                           uint64_t arena_bytes, const uint64_t* offs, uint64_t n, int32_t* verdicts,
-                           unsigned long long* hits, uint32_t stage, const KafkaCodecQueue& cq, const uint32_t* ids) {
+static hipError_t launch_k(const LaunchPlan& p, const BatchRef& b, const KafkaCodecQueue& cq) {
   const hipError_t e =
       set_lds_attr_once(reinterpret_cast<const void*>(kafka_eval_kernel<kHits, kAblate, kCliLds, kGroups>), kKLdsBytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((kafka_eval_kernel<kHits, kAblate, kCliLds, kGroups>), grid, dim3(kKBlock), lds, stream, dprog, arena,
-                     arena_bytes, offs, n, verdicts, hits, stage, cq.recs, cq.qhdr, cq.cap, ids);
+  hipLaunchKernelGGL((kafka_eval_kernel<kHits, kAblate, kCliLds, kGroups>), p.grid, dim3(kKBlock), p.lds, p.stream,
+                     p.dprog, b.arena, b.arena_bytes, b.offs, b.n, b.verdicts, b.hits, p.stage, cq.recs, cq.qhdr, cq.cap,
+                     b.ids);
   return hipGetLastError();
 }
 
 }  // namespace
 
-// Record stage of a Kafka workgroup (what the LDS leaves after the tables),
-// `reserve` bytes kept at the end.
-static size_t kafka_stage(const KafkaHeader& h, int mode, bool cli_lds, size_t reserve) {
+static size_t kafka_cli_words(const KafkaHeader& h) {
+  return static_cast<size_t>(h.n_clients) * (sizeof(KafkaClientSlot) / 4);
+}
+// Whether the client table is copied to LDS: there is one and it fits.
+static bool kafka_cli_lds(const KafkaHeader& h) {
+  return h.n_clients && kafka_cli_words(h) * 4 <= kMaxCliLdsBytes;
+}
+
+// LDS bytes of a Kafka workgroup besides its waves' record stages: tables,
+// the client table (cli_lds), hit counters (mode kKLdsHits), topic queues.
+static size_t kafka_fixed_lds(const KafkaHeader& h, int mode, bool cli_lds) {
   const uint32_t n_ctr = h.n_rules + 2;
-  const size_t cli_words = static_cast<size_t>(h.n_clients) * (sizeof(KafkaClientSlot) / 4);
-  const size_t fixed = 4u * (256u + kSpanLds + kKindOkLds + (cli_lds ? cli_words : 0u) +
-                             (mode == kKLdsHits ? ((n_ctr + 3u) & ~3u) : 0u)) +
-                       2u * kKWaves * 64 * kTopicQ;
+  return 4u * (256u + kSpanLds + kKindOkLds + (cli_lds ? kafka_cli_words(h) : 0u) +
+               (mode == kKLdsHits ? ((n_ctr + 3u) & ~3u) : 0u)) +
+         2u * kKWaves * 64 * kTopicQ;
+}
+
+// Record stage of a Kafka workgroup (what the LDS leaves after the fixed
+// part), `reserve` bytes kept at the end.
+static size_t kafka_stage(size_t fixed, size_t reserve) {
   size_t stage = (kKLdsBytes - reserve - fixed) / kKWaves - 16u;
   stage &= ~size_t(15);
   return stage > kKMaxStage ? kKMaxStage : stage;
 }
 
 bool kafka_resident_ok(const KafkaHeader& h, int* kind, uint32_t* stage) {
-  const size_t cli_words = static_cast<size_t>(h.n_clients) * (sizeof(KafkaClientSlot) / 4);
-  const bool cli_lds = cli_words && cli_words * 4 <= kMaxCliLdsBytes;
-  const size_t st = kafka_stage(h, kKNoHits, cli_lds, 4u * kResidentLdsWords);
+  const bool cli_lds = kafka_cli_lds(h);
+  const size_t st = kafka_stage(kafka_fixed_lds(h, kKNoHits, cli_lds), 4u * kResidentLdsWords);
   if (st < 1024) return false;
   *kind = static_cast<int>(kResidentKafka | (cli_lds ? 1u : 0u) | (h.n_id_slots ? 2u : 0u));
   *stage = static_cast<uint32_t>(st);
@@ -965,36 +975,24 @@ hipError_t launch_kafka_resident(ResidentBox* dbox, uint64_t first_seq, int kind
   });
 }
 
-hipError_t launch_kafka(const uint32_t* dprog, const KafkaHeader& h, const uint8_t* arena, uint64_t arena_bytes,
-                        const uint64_t* offs, uint64_t n, int32_t* verdicts, unsigned long long* hits,
-                        hipStream_t stream, int num_cus, uint32_t flags, const KafkaCodecQueue& cq,
-                        const uint32_t* ids) {
-  if (n == 0) return hipSuccess;
-  const uint32_t n_ctr = h.n_rules + 2;
-  const int mode = !hits ? kKNoHits : (n_ctr <= kKMaxLdsCounters ? kKLdsHits : kKGlobalHits);
-  const size_t cli_words = static_cast<size_t>(h.n_clients) * (sizeof(KafkaClientSlot) / 4);
-  const bool cli_lds = cli_words && cli_words * 4 <= kMaxCliLdsBytes;
-  const size_t fixed = 4u * (256u + kSpanLds + kKindOkLds + (cli_lds ? cli_words : 0u) +
-                             (mode == kKLdsHits ? ((n_ctr + 3u) & ~3u) : 0u)) +
-                       2u * kKWaves * 64 * kTopicQ;
-  const size_t stage = kafka_stage(h, mode, cli_lds, 0);
-  const size_t lds = fixed + kKWaves * (stage + 16u);
-  uint64_t blocks = static_cast<uint64_t>(num_cus > 0 ? num_cus : 256);
-  const uint64_t want = (n + 2 * kKBlock - 1) / (2 * kKBlock);
-  if (want < blocks) blocks = want;
-  const dim3 grid(static_cast<uint32_t>(blocks));
-  const uint32_t st = static_cast<uint32_t>(stage);
+hipError_t launch_kafka(const uint32_t* dprog, const KafkaHeader& h, const BatchRef& b, hipStream_t stream,
+                        int num_cus, uint32_t flags, const KafkaCodecQueue& cq) {
+  if (b.n == 0) return hipSuccess;
+  const int mode = !b.hits ? kKNoHits : (h.n_rules + 2 <= kKMaxLdsCounters ? kKLdsHits : kKGlobalHits);
+  const bool cli_lds = kafka_cli_lds(h);
+  const size_t fixed = kafka_fixed_lds(h, mode, cli_lds);
+  const size_t stage = kafka_stage(fixed, 0);
+  const LaunchPlan p{batch_grid(b.n, num_cus, kKBlock), fixed + kKWaves * (stage + 16u), static_cast<uint32_t>(stage),
+                     stream, dprog};
   if (flags & (L7M_FLAG_DIAG_COPY_ONLY | L7M_FLAG_DIAG_WALK_ONLY)) {
-    if (flags & L7M_FLAG_DIAG_COPY_ONLY)
-      return launch_k<kKNoHits, 1>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, st, cq, ids);
-    return launch_k<kKNoHits, 2>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, st, cq, ids);
+    if (flags & L7M_FLAG_DIAG_COPY_ONLY) return launch_k<kKNoHits, 1>(p, b, cq);
+    return launch_k<kKNoHits, 2>(p, b, cq);
   }
   const bool groups = h.n_id_slots != 0;
   return dispatch_values<int, kKNoHits, kKLdsHits, kKGlobalHits>(mode, hipErrorInvalidValue, [&](auto M) {
     return dispatch_values<bool, false, true>(cli_lds, hipErrorInvalidValue, [&](auto C) {
       return dispatch_values<bool, false, true>(groups, hipErrorInvalidValue, [&](auto G) {
-        return launch_k<decltype(M)::value, 0, decltype(C)::value, decltype(G)::value>(
-            grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, st, cq, ids);
+        return launch_k<decltype(M)::value, 0, decltype(C)::value, decltype(G)::value>(p, b, cq);
       });
     });
   });
@@ -1054,12 +1052,10 @@ __global__ __launch_bounds__(64) void kafka_codec_kernel(const uint32_t* __restr
 
 }  // namespace
 
-hipError_t launch_kafka_codec(const uint32_t* dprog, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs,
-                              uint64_t n, int32_t* verdicts, unsigned long long* hits, hipStream_t stream,
-                              const KafkaCodecQueue& cq) {
-  if (!cq.cap || !cq.workers || !n) return hipSuccess;
-  hipLaunchKernelGGL(kafka_codec_kernel, dim3(cq.workers), dim3(64), 0, stream, dprog, arena, offs, n, arena_bytes,
-                     cq.recs, cq.qhdr, cq.cap, verdicts, hits, cq.slabs, cq.slab_bytes);
+hipError_t launch_kafka_codec(const uint32_t* dprog, const BatchRef& b, hipStream_t stream, const KafkaCodecQueue& cq) {
+  if (!cq.cap || !cq.workers || !b.n) return hipSuccess;
+  hipLaunchKernelGGL(kafka_codec_kernel, dim3(cq.workers), dim3(64), 0, stream, dprog, b.arena, b.offs, b.n,
+                     b.arena_bytes, cq.recs, cq.qhdr, cq.cap, b.verdicts, b.hits, cq.slabs, cq.slab_bytes);
   return hipGetLastError();
 }
 

@@ -151,35 +151,31 @@ __global__ __launch_bounds__(kTileThreads) void kafka_side_emit(const uint8_t* a
 }
 
 template <bool kLog>
-hipError_t launch_kafka_side_as(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n,
-                                const int32_t* verdicts, uint32_t select, uint8_t* out, uint64_t cap,
-                                uint64_t* out_offs, uint64_t* total, hipStream_t stream) {
-  if (n == 0) {
+hipError_t launch_kafka_side_as(const BatchView& b, uint32_t select, uint8_t* out, uint64_t cap, uint64_t* out_offs,
+                                uint64_t* total, hipStream_t stream) {
+  if (b.n == 0) {
     hipError_t e = hipMemsetAsync(total, 0, sizeof(uint64_t), stream);
     if (e == hipSuccess && out_offs) e = hipMemsetAsync(out_offs, 0, sizeof(uint64_t), stream);
     return e;
   }
   return tile_pipeline(
-      n, {total}, 0, stream,
+      b.n, {total}, 0, stream,
       [&](uint32_t tiles, uint64_t* tile_sums, void*) {
-        kafka_side_measure<kLog><<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(arena, arena_bytes, offs, n, verdicts,
-                                                                                 select, out_offs, tile_sums);
+        kafka_side_measure<kLog><<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(
+            b.arena, b.arena_bytes, b.offs, b.n, b.verdicts, select, out_offs, tile_sums);
       },
       [&](uint32_t tiles, const uint64_t* tile_base, void*) {
-        kafka_side_emit<kLog><<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(arena, arena_bytes, offs, n, verdicts,
-                                                                              out, cap, out_offs, tile_base, total);
+        kafka_side_emit<kLog><<<dim3(tiles), dim3(kTileThreads), 0, stream>>>(
+            b.arena, b.arena_bytes, b.offs, b.n, b.verdicts, out, cap, out_offs, tile_base, total);
       });
 }
 
 }  // namespace
 
-hipError_t launch_kafka_side(bool log, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n,
-                             const int32_t* verdicts, uint32_t select, uint8_t* out, uint64_t cap,
+hipError_t launch_kafka_side(bool log, const BatchView& b, uint32_t select, uint8_t* out, uint64_t cap,
                              uint64_t* out_offs, uint64_t* total, hipStream_t stream) {
-  return log ? launch_kafka_side_as<true>(arena, arena_bytes, offs, n, verdicts, select, out, cap, out_offs, total,
-                                          stream)
-             : launch_kafka_side_as<false>(arena, arena_bytes, offs, n, verdicts, select, out, cap, out_offs, total,
-                                           stream);
+  return log ? launch_kafka_side_as<true>(b, select, out, cap, out_offs, total, stream)
+             : launch_kafka_side_as<false>(b, select, out, cap, out_offs, total, stream);
 }
 
 }  // namespace l7m

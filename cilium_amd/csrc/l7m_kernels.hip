@@ -26,28 +26,6 @@
 
 namespace l7m {
 
-// First-pass / slow-pass launches of the ECMAScript instantiations of one
-// feature set (l7m_http_feat.hip, compiled once per kFeat)
-#define L7M_FEAT_DECL(F)                                                                                            \
-  hipError_t launch_http_main_f##F(int mode, int R, bool lean, dim3 grid, size_t lds, hipStream_t stream,              \
-                                   const uint32_t* dprog,                                                              \
-                                   const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs, uint64_t n,        \
-                                   int32_t* verdicts, unsigned long long* hits, uint32_t stage, uint32_t* slowq,       \
-                                   DoneSignal done);                                                                   \
-  hipError_t launch_http_slow_f##F(int R, int tier, const HttpHeader& h, uint32_t blocks, hipStream_t stream,         \
-                                   const uint32_t* dprog, const uint8_t* arena, uint64_t arena_bytes,                  \
-                                   const uint64_t* offs, uint64_t n, int32_t* verdicts, unsigned long long* hits,      \
-                                   const uint32_t* slowq, uint32_t* slowq2, uint32_t* vmscratch, uint32_t* work);
-L7M_FEAT_DECL(0)
-L7M_FEAT_DECL(1)
-L7M_FEAT_DECL(2)
-L7M_FEAT_DECL(3)
-L7M_FEAT_DECL(4)
-L7M_FEAT_DECL(5)
-L7M_FEAT_DECL(6)
-L7M_FEAT_DECL(7)
-#undef L7M_FEAT_DECL
-
 size_t http_lds_bytes(const HttpHeader& h, uint32_t stage) {
   const bool reg = h.n_dfas <= kRegDfas || h.search;  // search programs: codes in global scratch
   const size_t ctr = h.n_rules + 2 <= kMaxLdsCounters ? ((h.n_rules + 2 + 3) & ~size_t(3)) : 0;
@@ -68,40 +46,33 @@ hipError_t launch_resident(ResidentBox* dbox, uint64_t first_seq, int kind, uint
   return launch_kafka_resident(dbox, first_seq, kind, qhdr, stream);
 }
 
-hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t* arena, uint64_t arena_bytes,
-                       const uint64_t* offs, uint64_t n, int32_t* verdicts, unsigned long long* hits,
-                       hipStream_t stream, int num_cus, uint32_t flags, const DoneSignal* done) {
+hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const BatchRef& b, hipStream_t stream, int num_cus,
+                       uint32_t flags, const DoneSignal* done) {
+  const uint64_t n = b.n;
   if (n == 0) return hipSuccess;
   const uint32_t stage = http_stage_bytes(h);
   if (stage == 0) return hipErrorInvalidValue;
-  const size_t lds = http_lds_bytes(h, stage);
-  // kHttpWgPerCu resident workgroups per CU (1 by default); fewer for small
-  // batches (>= 2 records per lane, two tiles per wave).
-  uint64_t blocks = static_cast<uint64_t>(num_cus > 0 ? num_cus : 256) * kHttpWgPerCu;
-  const uint64_t want = (n + 2 * kBlock - 1) / (2 * kBlock);
-  if (want < blocks) blocks = want;
-  const dim3 grid(static_cast<uint32_t>(blocks));
+  // kHttpWgPerCu resident workgroups per CU (1 by default)
+  const LaunchPlan p{batch_grid(n, num_cus, kBlock, kHttpWgPerCu), http_lds_bytes(h, stage), stage, stream, dprog};
   const bool reg = h.n_dfas <= kRegDfas;
   if (flags & (L7M_FLAG_DIAG_WALK_ONLY | L7M_FLAG_DIAG_COPY_ONLY)) {  // diagnostic ablations
     // (register end codes only; no search or dense automata, no slow-path queue)
     if (!reg || h.search || h.n_slow || (flags & kLaunchDense)) return hipErrorInvalidValue;
-    if (flags & L7M_FLAG_DIAG_COPY_ONLY)
-      return launch_one<kNoHits, 8, 2>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, stage);
-    return launch_one<kNoHits, 8, 1>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits, stage);
+    if (flags & L7M_FLAG_DIAG_COPY_ONLY) return launch_one<kNoHits, 8, 2>(p, b);
+    return launch_one<kNoHits, 8, 1>(p, b);
   }
-  const int mode = !hits ? kNoHits : (h.n_rules + 2 <= kMaxLdsCounters ? kLdsHits : kGlobalHits);
+  const int mode = !b.hits ? kNoHits : (h.n_rules + 2 <= kMaxLdsCounters ? kLdsHits : kGlobalHits);
   if (h.search) {
     // RE2-dialect programs (search automata, program.h kDfaSearch): their own
     // instantiation, end codes in a stream-ordered global scratch column per
     // thread (n_dfas words each)
     uint32_t* scratch = nullptr;
-    const size_t bytes = static_cast<size_t>(h.n_dfas ? h.n_dfas : 1) * grid.x * kBlock * 4u;
+    const size_t bytes = static_cast<size_t>(h.n_dfas ? h.n_dfas : 1) * p.grid.x * kBlock * 4u;
     hipError_t e = scratch_alloc_async(reinterpret_cast<void**>(&scratch), bytes, stream);
     if (e != hipSuccess) return e;
     const DoneSignal sig = done ? *done : DoneSignal{nullptr, nullptr, 0};
     e = dispatch_values<int, kNoHits, kLdsHits, kGlobalHits>(mode, hipErrorInvalidValue, [&](auto M) {
-      return launch_one<decltype(M)::value, -1>(grid, lds, stream, dprog, arena, arena_bytes, offs, n, verdicts, hits,
-                                                stage, scratch, nullptr, sig);
+      return launch_one<decltype(M)::value, -1>(p, b, scratch, nullptr, sig);
     });
     const hipError_t e2 = hipFreeAsync(scratch, stream);
     return e != hipSuccess ? e : e2;
@@ -112,21 +83,17 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
   // programs with slow-path rules (program.h kCrSlow): the first pass queues
   // the requests they may decide, http_slow_kernel decides them; the queue
   // (count + up to n indices) and the executor scratch are stream-ordered
-  uint32_t* slowq = nullptr;
-  uint32_t* slowq2 = nullptr;
-  uint32_t* vms = nullptr;
-  uint32_t* vms2 = nullptr;
-  uint32_t* work = nullptr;  // [0] tier-1, [64] tier-2 work counters
+  HttpSlowPass s;
   const size_t qbytes = (4ull * (n + 1) + 255) & ~size_t(255);
   // tier 1: kSlowWavesPerCu waves per CU (fewer for small batches), tier 2: kSlowBlocks2 waves
   const uint64_t waves = (n + kSlowBlock - 1) / kSlowBlock;
   const uint64_t w1 = static_cast<uint64_t>(num_cus > 0 ? num_cus : 256) * kSlowWavesPerCu;
-  const uint32_t blocks1 = static_cast<uint32_t>(waves < w1 ? waves : w1);
-  const uint32_t blocks2 = static_cast<uint32_t>(waves < kSlowBlocks2 ? waves : kSlowBlocks2);
+  s.blocks[0] = static_cast<uint32_t>(waves < w1 ? waves : w1);
+  s.blocks[1] = static_cast<uint32_t>(waves < kSlowBlocks2 ? waves : kSlowBlocks2);
   void* buf = nullptr;  // the one stream-ordered allocation of the slow pass (freed by its base)
   if (h.n_slow) {
-    const size_t v1 = static_cast<size_t>(blocks1) * kSlowBlock * kVmScratchWords * 4u;
-    const size_t v2 = static_cast<size_t>(blocks2) * kSlowBlock * kVmScratchWords2 * 4u;
+    const size_t v1 = static_cast<size_t>(s.blocks[0]) * kSlowBlock * kVmScratchWords * 4u;
+    const size_t v2 = static_cast<size_t>(s.blocks[1]) * kSlowBlock * kVmScratchWords2 * 4u;
     hipError_t e = scratch_alloc_async(&buf, 512 + 2 * qbytes + v1 + v2, stream);
     if (e == hipSuccess) e = hipMemsetAsync(buf, 0, 512, stream);
     if (e == hipSuccess) e = hipMemsetAsync(static_cast<uint8_t*>(buf) + 512, 0, 4, stream);
@@ -135,34 +102,27 @@ hipError_t launch_http(const uint32_t* dprog, const HttpHeader& h, const uint8_t
       if (buf) (void)hipFreeAsync(buf, stream);
       return e;
     }
-    work = static_cast<uint32_t*>(buf);
-    slowq = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + 512);
-    slowq2 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + 512 + qbytes);
-    vms = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + 512 + 2 * qbytes);
-    vms2 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + 512 + 2 * qbytes + v1);
+    s.work = static_cast<uint32_t*>(buf);
+    s.slowq = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + 512);
+    s.slowq2 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + 512 + qbytes);
+    s.vms[0] = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + 512 + 2 * qbytes);
+    s.vms[1] = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + 512 + 2 * qbytes + v1);
   }
   // the instantiation with the program's features (literal tables, forced
   // captures, dense automata); l7m_http_feat.hip compiles one translation
   // unit per literal / capture set, holding it and its dense twin (+ 4)
   const int feat = (lit ? kFeatLit : 0) | (h.lds_dcap != kNone ? kFeatDcap : 0) |
                    ((flags & kLaunchDense) ? kFeatDense : 0);
-  static decltype(&launch_http_main_f0) const mains[8] = {launch_http_main_f0, launch_http_main_f1,
-                                                           launch_http_main_f2, launch_http_main_f3,
-                                                           launch_http_main_f4, launch_http_main_f5,
-                                                           launch_http_main_f6, launch_http_main_f7};
-  static decltype(&launch_http_slow_f0) const slows[8] = {launch_http_slow_f0, launch_http_slow_f1,
-                                                           launch_http_slow_f2, launch_http_slow_f3,
-                                                           launch_http_slow_f4, launch_http_slow_f5,
-                                                           launch_http_slow_f6, launch_http_slow_f7};
   // the completion signal only where this launch decides every request
   const DoneSignal sig = done && !h.n_slow ? *done : DoneSignal{nullptr, nullptr, 0};
-  // (kLaunchLean: the lean kernels of the plain feature set; an error for any other)
-  hipError_t e = mains[feat](mode, R, (flags & kLaunchLean) != 0, grid, lds, stream, dprog, arena, arena_bytes, offs, n,
-                             verdicts, hits, stage, slowq, sig);
+  const bool lean = (flags & kLaunchLean) != 0;  // the lean kernels of the plain feature set; an error for any other
+  hipError_t e = dispatch_values<int, 0, 1, 2, 3, 4, 5, 6, 7>(feat, hipErrorInvalidValue, [&](auto F) {
+    hipError_t r = launch_http_main<decltype(F)::value>(p, b, mode, R, lean, s.slowq, sig);
+    for (int tier = 1; h.n_slow && tier <= 2 && r == hipSuccess; ++tier)
+      r = launch_http_slow<decltype(F)::value>(p, h, b, s, R, tier);
+    return r;
+  });
   if (h.n_slow) {
-    for (int tier = 1; tier <= 2 && e == hipSuccess; ++tier)
-      e = slows[feat](R, tier, h, tier == 1 ? blocks1 : blocks2, stream, dprog, arena, arena_bytes, offs, n, verdicts,
-                      hits, slowq, slowq2, tier == 1 ? vms : vms2, work + (tier - 1) * 64);
     const hipError_t e2 = hipFreeAsync(buf, stream);
     if (e == hipSuccess) e = e2;
   }
