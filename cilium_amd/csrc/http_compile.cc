@@ -1297,6 +1297,7 @@ CompileResult compile_http_core(const l7m_http_rule* rules, size_t n, const Poli
   uint32_t* I = P + h.lds_image_off;
   uint16_t* I16 = reinterpret_cast<uint16_t*>(I);
   std::memcpy(P, &h, sizeof h);
+  bool inline_masks = true;  // CandEntry::pad decides every inline code matcher (program.h kHttpInlineMasks)
   for (uint32_t k = 0; k < ndt; ++k) {
     const PackedDfa& d = *all[k].d;
     if (dd[k].kind == kDfaSearch) {
@@ -1330,6 +1331,17 @@ CompileResult compile_http_core(const l7m_http_rule* rules, size_t n, const Poli
         const uint32_t nm = cr_matchers(cr[sp.off + 1]);
         const uint32_t words = 2 + 2 * std::min(nm, kCandInlineMatchers);
         std::memcpy(ce[i].rec, cr.data() + sp.off, words * 4);
+        // An inlined first record: pad[q] decides inline code matcher q from
+        // its automaton's set code without a mask table (bit s: set s holds the
+        // matcher's pattern), exact when that automaton has <= 32 sets.
+        for (uint32_t q = 0; nm <= kCandInlineMatchers && q < nm; ++q) {
+          const uint32_t a = ce[i].rec[2 + 2 * q], pat = ce[i].rec[3 + 2 * q] & kPatMask;
+          if ((a >> 8) & 1u) continue;  // a presence matcher
+          const auto& msets = all[a >> 9].d->sets;
+          if (msets.size() > 32) inline_masks = false;
+          for (size_t s2 = 0; s2 < msets.size() && s2 < 32; ++s2)
+            if (std::find(msets[s2].begin(), msets[s2].end(), pat) != msets[s2].end()) ce[i].pad[q] |= 1u << s2;
+        }
         P[dd[k].ctmask_off + i / 32] |= 1u << (i % 32);
         if (dd[k].lds_ctmask != kNone) I[dd[k].lds_ctmask + i / 32] |= 1u << (i % 32);
       }
@@ -1367,6 +1379,10 @@ CompileResult compile_http_core(const l7m_http_rule* rules, size_t n, const Poli
     if (dd[k].lds_ct != kNone) std::memcpy(I + dd[k].lds_ct, ce.data(), ce.size() * sizeof(CandEntry));
     if (dd[k].lds_mask != kNone) std::memcpy(I + dd[k].lds_mask, masks[k].data(), masks[k].size() * 8);
   }
+  // (a bit of single_entry, so single-entry programs alone carry it: the lean kernel's; the
+  // header was copied before the entries were filled)
+  if (inline_masks && h.single_entry) h.single_entry |= kHttpInlineMasks;
+  std::memcpy(P, &h, sizeof h);
   std::memcpy(P + h.off_dfas, dd.data(), dd.size() * sizeof(DfaDesc));
   std::memcpy(I + lds_dfas, dd.data(), dd.size() * sizeof(DfaDesc));
   for (size_t k = 0; k < dcaps.size(); ++k) {

@@ -1046,6 +1046,7 @@ struct LeanHeader {
   uint32_t cand_dfas_lo, pres_fields_lo, pres_fields_hi, always_rule;
   Span zero_list;
   LeanJob j0, j1, j2;
+  uint32_t inline_masks;  // program.h kHttpInlineMasks: CandEntry::pad decides the inline code matchers
   // job J's automaton, every member a scalar
   template <int J>
   __device__ __forceinline__ JobDfa job() const {
@@ -1100,6 +1101,7 @@ __device__ __forceinline__ LeanHeader make_lean_header(const HttpHeader& h, cons
   l.j0 = make_lean_job(c, 0, l.cand_dfas_lo);
   l.j1 = make_lean_job(c, 1, l.cand_dfas_lo);
   l.j2 = make_lean_job(c, 2, l.cand_dfas_lo);
+  l.inline_masks = keep_scalar(h.single_entry & kHttpInlineMasks);
   return l;
 }
 // The header the tile loop reads: the program's, or the lean kernel's copy.
@@ -1521,13 +1523,34 @@ __device__ __forceinline__ int32_t eval_verify(const Ctx& c, const H& h, const W
   };
   // Candidates of each DFA end code: one 64-byte CandEntry whose first check
   // record is inline; longer lists fall back to the pool scan.
-  auto check_entry = [&](const u32x4 q0, const u32x4 q1, const u32x4 q2) {  // a CandEntry's first 48 bytes
+  // (q3, CandEntry::pad: the lean kernel only)
+  auto check_entry = [&](const u32x4 q0, const u32x4 q1, const u32x4 q2, const u32x4 q3) {  // a CandEntry
     const uint32_t len = q0.x, rid = q0.z, hd = q0.w, nm = cr_matchers(hd);  // len, off, rid, hdr
     if (len == 1 && nm <= kCandInlineMatchers) {
       if (rid >= best) return;
       const uint32_t ma[4] = {q1.x, q1.z, q2.x, q2.z}, mp[4] = {q1.y, q1.w, q2.y, q2.w};
       bool ok = eligible(hd) && (!(hd & kCrRemote) || remote_ok(rid));
-      if constexpr (kReg < 0) {  // search programs (mask codes): one matcher after the other
+      bool decided = false;
+      if constexpr (kLean) {
+        // The inline matchers from the entry alone when the program says its
+        // pad words are exact (kHttpInlineMasks, wave-uniform): a latched code
+        // by compare, a set code by its bit of pad[q] (set codes are < 32
+        // then), code 0 fails.  No LDS read and no wait; programs without the
+        // flag take the two rounds below.
+        if (h.inline_masks) {
+          const uint32_t mk[4] = {q3.x, q3.y, q3.z, q3.w};
+#pragma unroll
+          for (uint32_t q = 0; q < kCandInlineMatchers; ++q) {
+            const uint32_t a = ma[q], cq = codes.get(a >> 9);
+            const bool pres = ((present >> (a & 0xffu)) & 1ull) != 0;
+            const bool hit = (cq & kLatchedBit) ? (cq & ~kLatchedBit) == mp[q] : ((mk[q] >> (cq & 31u)) & (cq != 0)) != 0;
+            ok = ok && (q >= nm || (pres && (((a >> 8) & 1u) || hit)));
+          }
+          decided = true;
+        }
+      }
+      if (decided) {
+      } else if constexpr (kReg < 0) {  // search programs (mask codes): one matcher after the other
 #pragma unroll
         for (uint32_t q = 0; q < kCandInlineMatchers; ++q) {
           if (q < nm && ok) {
@@ -1584,7 +1607,7 @@ __device__ __forceinline__ int32_t eval_verify(const Ctx& c, const H& h, const W
   };
   auto check_inline = [&](const uint32_t* e) {  // e -> CandEntry in LDS
     const u32x4* q = reinterpret_cast<const u32x4*>(e);
-    check_entry(q[0], q[1], q[2]);
+    check_entry(q[0], q[1], q[2], kLean ? q[3] : u32x4{});
   };
   // only DFAs with candidate entries (search programs: only those the record
   // set a code for -- a handful of dozens)
@@ -1612,7 +1635,7 @@ __device__ __forceinline__ int32_t eval_verify(const Ctx& c, const H& h, const W
           const gq q = (gq)(c.prog + dd.ct_off + 16u * idx);
           u32x4 q0 = q[0], q1 = q[1], q2 = q[2];
           asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2));
-          check_entry(q0, q1, q2);
+          check_entry(q0, q1, q2, u32x4{});
         }
       }
       continue;
@@ -1626,9 +1649,10 @@ __device__ __forceinline__ int32_t eval_verify(const Ctx& c, const H& h, const W
     } else {  // an HBM candidate entry (touched by the walk phase)
       typedef __attribute__((address_space(1))) const u32x4* gq;
       const gq q = (gq)(c.prog + dd.ct_off + 16u * idx);
-      u32x4 q0 = q[0], q1 = q[1], q2 = q[2];
+      u32x4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = kLean ? q[3] : u32x4{};
       asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2));
-      check_entry(q0, q1, q2);
+      if constexpr (kLean) asm volatile("" : "+v"(q3));
+      check_entry(q0, q1, q2, q3);
     }
   }
   for (uint64_t pm = ((static_cast<uint64_t>(h.pres_fields_hi) << 32) | h.pres_fields_lo) & present; pm;
@@ -1817,9 +1841,24 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
     issue_bytes(t);
   }
   load_offs(t.cur + t.take, &o2, &n2);
+  // Lean kernel: a tile's verdicts are stored one tile late.  Every LDS access
+  // that may alias the stage waits for vmcnt(0), which on this target also
+  // counts stores: stored where it is computed, the verdict's acknowledgement
+  // (nobody in the kernel reads it) is waited for by the counter adds and the
+  // next top-of-loop wait a few dozen cycles later.  Held in registers (held_v,
+  // kNeedVerify in lanes without a record: no verdict has that value) and
+  // stored right after the next tile's top wait, the acknowledgement returns
+  // under that tile's walks; the last tile's are stored after the loop, before
+  // the counter flush and the DoneSignal fences.
+  int32_t held_v = kNeedVerify;
+  uint64_t held_at = 0;
+  auto store_held = [&]() {
+    if (held_v != kNeedVerify) verdicts[held_at] = held_v;
+  };
   while (t.cur < end) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tile's LDS-DMA pieces have landed
     wave_sync();
+    if constexpr (kLean) store_held();  // the previous tile's verdicts
     qtn(0);
 
     const uint64_t o = t.o, onext = t.onext, base = t.base;
@@ -1859,7 +1898,7 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
     qtn(3);
     if (lane < take) {
       if (v == kNeedVerify) v = eval_verify<kReg, 0, (kFeat & kFeatDcap) != 0>(c, th, wo);
-      verdicts[t.cur + lane] = v;
+      if constexpr (!kLean) verdicts[t.cur + lane] = v;
       if (v == kDeferred) {  // decided by http_slow_kernel (rules with slow-path matchers)
         const uint32_t at = atomicAdd(slowq, 1u);
         slowq[1 + at] = static_cast<uint32_t>(t.cur + lane);
@@ -1885,6 +1924,16 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
         count_slot(hits, slot, slot != kNone);
       }
     }
+    if constexpr (kLean) {
+      held_v = lane < take ? v : kNeedVerify;
+      held_at = t.cur + lane;
+    }
+    // The stage's readers are ordered without this fence: tile t's stage reads
+    // precede the DMA of t + 1 by the lgkmcnt(0) in issue_bytes, the DMA
+    // precedes tile t + 1's reads by the top wait and its fence, and the LDS
+    // counter adds need no order before the __syncthreads() of the flush.  It
+    // emits no instruction; it stays as the compiler-level barrier that keeps
+    // the counter adds inside their iteration (and so before that flush).
     wave_sync();  // the stage is overwritten by the next tile
     t = t2;
     qtn(5);
@@ -1910,6 +1959,7 @@ __device__ __forceinline__ void http_eval_body(const uint32_t* __restrict__ prog
              (unsigned long long)prof[4], (unsigned long long)prof[5], (unsigned long long)prof[6],
              (unsigned long long)prof[7]);
   }
+  if constexpr (kLean) store_held();  // the last tile's verdicts
   if (kHits == kLdsHits) {
     __syncthreads();
     for (uint32_t i = tid; i < n_ctr; i += kBlock) {

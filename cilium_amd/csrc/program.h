@@ -127,7 +127,9 @@ struct CandEntry {
   uint32_t len;       // number of check records (0 = no candidate)
   uint32_t off;       // word offset of the first record in the pool
   uint32_t rec[10];   // first record: rid, header, up to 4 x (matcher, pattern)
-  uint32_t pad[4];
+  uint32_t pad[4];    // first record inlined whole: pad[q] bit s (s < 32) = set code s of inline code
+                      // matcher q's automaton holds the matcher's pattern (else 0); read by the lean
+                      // HTTP kernel when the header says kHttpInlineMasks
 };
 static_assert(sizeof(CandEntry) == 64, "cand entry is 16 words");
 constexpr uint32_t kLatchedBit = 0x80000000u;
@@ -284,7 +286,8 @@ struct HttpHeader {
   uint32_t total_words;
   uint32_t lds_name_tab;   // LDS image offset of the header-name table, or kNone
   uint32_t name_tab_mask;  // its slot count - 1 (power of two)
-  uint32_t single_entry;   // 1: every policy-0 request uses entry 0 (l7m_compile_http)
+  uint32_t single_entry;   // bit 0: every policy-0 request uses entry 0 (l7m_compile_http);
+                           // bit 1 (kHttpInlineMasks): see below.  Read it as zero / non-zero, or by bit.
   uint32_t n_policies;     // endpoint policies (record policy field < n_policies)
   uint32_t ent_tab_off;    // program: port-entry table
   uint32_t lds_ent_tab;    // LDS image copy, or kNone
@@ -301,6 +304,11 @@ struct HttpHeader {
                            // rules with kCrSlow matchers (regex_vm.h), or kNone
   uint32_t n_slow;         // rules with slow-path matchers
 };
+// HttpHeader::single_entry bit 1: every automaton that an inline code matcher
+// of a candidate entry targets has <= 32 sets, so CandEntry::pad decides every
+// such matcher exactly.  Without it a reader of pad must not trust it.  Only
+// single-entry programs carry it (bit 0 is set too): the word stays zero otherwise.
+constexpr uint32_t kHttpInlineMasks = 2u;
 // Header-name table (LDS image): exact lower-case header names of the rules
 // -> field id, open addressing on the program.h name hash; slot =
 // {hash (0 = empty), len, field, image word offset of the zero-padded name}.
